@@ -8,13 +8,20 @@ fixed-length-episode env (no gymnasium on the box).  A "step" is
 reference epoch: one rollout of 4096 x 32 env steps (policy forward + sample + env step
 per vector step, bootstrap value, GAE) followed by the whole PPO update over it.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
 
 Multi-GPU: weak scaling — every rank owns its own 4096 envs (global env ids offset by
 rank), runs its own sampler stream, and the flat gradient is all-reduced (RCCL, mean)
 once per minibatch step before the norm clip.  value = all ranks' env steps / max-rank time.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times its K steps and prints the line (value, ms_per_step, the
+phase times of the timed steps).  --full adds, from runs of their own after the timed steps, the
+per-kernel stage times and rooflines, the exchange launch, the bf16 mode's deviation from fp32 and
+the CPU baseline.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(same arguments, same seeds: two builds can be compared array for array); in a multi-GPU run
+rank 0 alone writes, its own arrays.
 """
 from __future__ import annotations
 
@@ -34,6 +41,8 @@ import torch  # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: dense f32 MFMA (= f32 vector peak)
 PEAK_HBM_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E spec
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: ~2.5 PF dense bf16 (no sparsity)
+DUMP_MAX_ELEMS = 1 << 20       # --dump-outputs: elements written per array (4 MB of float32)
+DUMP_SAMPLE_SEED = 0           # ... and the seed of the sample taken from a larger one
 # CPU port vs the reference's own loop on the same 8-core container at C2 shapes: port / reference, re-derived in round 6 on the build container (tools/cpu_calibration.py: the
 # reference's own C2 loop, imported from /root/reference, and the port alternated in 24 blocks of 50
 # minibatches on the same 8 threads, medians; 4 runs gave 0.90 / 1.36 / 1.18 / 1.06 on this shared
@@ -348,135 +357,38 @@ def launch_ranks(n: int, argv, script: str = None, poll_s: float = 0.2) -> int:
     return rc
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--workload", choices=tuple(WORKLOADS), default="C2",
-                    help="C2: CartPole-v1:ppo (the metric's config); C3: LunarLander-v3:ppo shapes (T=2048, B=64); "
-                         "C4/C5: ALE Pong/Breakout rgb_ppo (NatureCNN, Atari pixel pipeline)")
-    ap.add_argument("--env-dynamics", choices=("synthetic", "cartpole"), default="synthetic",
-                    help="MLP workloads: SURVEY §8d synthetic fixed-length episodes (default) or device CartPole-v1")
-    ap.add_argument("--n-envs", type=int, default=None, help="envs per GPU (weak scaling; default per workload)")
-    ap.add_argument("--no-graph", action="store_true", help="eager launches instead of the hipGraph")
-    ap.add_argument("--local-comm", action="store_true",
-                    help="N=1 only: run the multi-GPU chain through a one-rank communicator")
-    ap.add_argument("--comm", choices=("xgmi", "rccl"), default="xgmi",
-                    help="gradient-exchange transport for N>1 (and --local-comm): one-shot xGMI or RCCL")
-    ap.add_argument("--same-device", action="store_true",
-                    help="rehearsal on a one-GPU box: all ranks share cuda:0 (gloo process group, "
-                         "xGMI exchange through same-device IPC); throughput is not meaningful")
-    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
-                    help="f32: the fp32 parity path (default, the metric's line); bf16: bf16 MFMA operands in the "
-                         "update (the MLP's fused chain, the NatureCNN's convolutions / GEMMs), reported as its own "
-                         "line with its deviation from fp32 over one whole update")
-    ap.add_argument("--dp-mode", choices=("local", "global"), default="local",
-                    help="N>1: local (each rank's own minibatches, gradients averaged: the default) or global (the "
-                         "reference's exact global minibatches split over the ranks, sums exchanged)")
-    ap.add_argument("--stage-reps", type=int, default=200)
-    ap.add_argument("--cpu-minibatches", type=int, default=-1,
-                    help="minibatches timed in the CPU baseline (-1: the whole update, 0: no CPU baseline)")
-    args = ap.parse_args()
-    if args.gpus < 1:
-        ap.error("--gpus must be >= 1")
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # no launcher around us: start one rank per GPU ourselves (before any GPU call)
-        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world != args.gpus:
-        raise SystemExit(f"[bench] WORLD_SIZE={world} but --gpus {args.gpus}: they must agree")
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    dev_index = 0 if args.same_device else local_rank
-    torch.cuda.set_device(dev_index)
-    device = torch.device(f"cuda:{dev_index}")
-    if world > 1:
-        import torch.distributed as dist
-        if args.same_device:          # rehearsal: every rank on cuda:0, host-side process group
-            dist.init_process_group("gloo", rank=rank, world_size=world)
+def dump_outputs(agent, out_dir: str) -> None:
+    """--dump-outputs: what the last timed train_epoch() left for its caller, one float32
+    <name>.npy each: the flat parameters and Adam moments after the update, the update's
+    per-minibatch metric records, and the rollout the update trained on (time-major (T, N)
+    fields).  An array above DUMP_MAX_ELEMS elements is written as a fixed, seeded sample of its
+    flattened elements (the pixel workloads' frame stacks), so a dump stays far below 64 MB.
+    main() calls it on rank 0 only: a multi-GPU run dumps that rank's rollout and records."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    buf = agent.get_rollout_collector("train").buffer
+    arrays = {"params": agent.policy_model.params, "adam_m": agent.adam_m, "adam_v": agent.adam_v,
+              "minibatch_metrics": agent.metrics_buf,
+              "rollout_obs": buf.obs, "rollout_actions": buf.actions, "rollout_logprobs": buf.logprobs,
+              "rollout_values": buf.values, "rollout_rewards": buf.rewards, "rollout_dones": buf.dones,
+              "rollout_advantages": buf.advantages, "rollout_returns": buf.returns,
+              "rollout_last_values": buf.last_values}
+    for name, t in arrays.items():      # .cpu() is ordered after the update on the launch stream
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            pick = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, flat.numel(), DUMP_MAX_ELEMS))
+            a = flat[torch.from_numpy(pick).to(flat.device)].to(torch.float32).cpu().numpy()
         else:
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
+            a = t.detach().to(torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
-    from gsamd.config import load_config
-    from gsamd.ppo_agent import DevicePPOAgent
-    torch.manual_seed(42)
-    env_id, variant, n_default = WORKLOADS[args.workload]
-    pixel = variant == "rgb_ppo"
-    n_envs = args.n_envs or n_default
-    # the benchmark's env is chosen explicitly: SURVEY §8d synthetic fixed-length episodes (or the
-    # synthetic Atari frame source), or the device CartPole-v1 dynamics
-    over = dict(n_envs=n_envs, env_dynamics="synthetic" if pixel else args.env_dynamics)
-    if args.dtype == "bf16":
-        over["precision"] = "bf16"
-    if args.dp_mode == "global":
-        over["dp_mode"] = "global"
-    cfg = load_config(env_id, variant, overrides=over)
-    agent = DevicePPOAgent(cfg, device=device, rank=rank, world_size=world,
-                           use_graph=not args.no_graph, track_stats=False)
-    comm = None
-    if world > 1 or args.local_comm:      # sized to this policy's flat gradient
-        from gsamd import distributed as gd
-        n_params = agent.policy_model.n_params
-        if world == 1:
-            comm = gd.init_local_comm(args.comm, n_params)
-        elif args.comm == "xgmi":
-            try:
-                # MLP: the in-backward exchange is checked on this job's shapes before the timed run
-                comm = gd.init_xgmi_comm(rank, world, n_params, device,
-                                         verify_shapes=None if pixel else (agent.policy_model.dims, cfg.batch_size,
-                                                                           int(agent.hparams().flags)))
-            except RuntimeError as e:     # every rank raises together: switch transport together
-                _log(f"[bench] {e}; using RCCL for the gradient exchange")
-                args.comm = "rccl (xgmi unavailable)"
-                comm = gd.init_device_comm(rank, world, device)
-        else:
-            comm = gd.init_device_comm(rank, world, device)
-        agent.comm = comm
-    comm_info = None
-    from gsamd.distributed import LAST_SELF_TEST as gd_self_test
-    if comm is not None:
-        from gsamd.distributed import comm_info as _comm_info
-        comm_info = _comm_info(comm)
-        if comm_info["nranks"] != world or comm_info["rank"] != rank:
-            raise RuntimeError(f"communicator reports {comm_info}, launcher says rank {rank} of {world}")
+
+def full_measurements(args, agent, cfg, comm, in_bwd, world, rank, device, barrier, update_ms) -> dict:
+    """--full: what the bench line reports beside its headline figure, each from runs of its own
+    after the timed steps: per-kernel stage times and rooflines, the gradient exchange's launch,
+    the bf16 mode's deviation from fp32 over one update, and the CPU baseline."""
+    pixel = agent.is_pixel
     N, T = cfg.n_envs, cfg.n_steps
-
-    def barrier():
-        torch.cuda.synchronize()
-        if world > 1:
-            torch.distributed.barrier()
-        torch.cuda.synchronize()
-
-    if args.warmup < 2 and not args.no_graph:
-        _log("[bench] warning: --warmup < 2 times the rollout graph's capture (second collect)")
-    tw = time.perf_counter()
-    for _ in range(args.warmup):
-        agent.train_epoch()
-    barrier()
-    _log(f"[bench] rank {rank}: warmup {args.warmup} steps {time.perf_counter() - tw:.2f}s")
-    agent.phase_events = []
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        agent.train_epoch()
-    barrier()
-    elapsed = time.perf_counter() - t0
-    phases = agent.phase_events
-    agent.phase_events = None
-    collect_ms = sum(e[0].elapsed_time(e[1]) for e in phases) / len(phases)
-    update_ms = sum(e[1].elapsed_time(e[2]) for e in phases) / len(phases)
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.same_device else device)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed = float(t.item())
-    losses = agent.minibatch_losses()
-    if not (losses == losses).all():
-        raise RuntimeError("non-finite loss in the timed region")
-    total_env_steps = world * N * T * args.steps
-    value = total_env_steps / elapsed
-    ms_per_step = elapsed / args.steps * 1e3
-
     # ---- roofline of the dominant minibatch kernel (device time by events) ----
     pm = agent.policy_model
     stage_us = {}
@@ -522,11 +434,7 @@ def main():
     # in-kernel stamps) at 2.4 GHz — bit-exact parity forbids splitting T
     rooflines["gae"]["serial_bound_us"] = round(gT * 24 / 2.4e3, 3)
     rooflines["gae"]["serial_frac"] = round(gT * 24 / 2.4e3 / gae_us, 4) if gae_us > 0 else None
-    in_bwd = None
     if comm is not None:       # every rank takes part (the exchange is collective)
-        if not pixel:
-            from gsamd.distributed import exchange_inside_bwd
-            in_bwd = exchange_inside_bwd(comm, pm.dims, cfg.batch_size)
         # the exchange as its own launch (what the chain runs after k_bwd unless in_bwd)
         stage_us["exchange_launch" if in_bwd else "exchange"] = time_exchange(comm, pm.n_params, args.stage_reps,
                                                                                device, barrier)
@@ -638,6 +546,162 @@ def main():
                "calibration": ("the port omits the reference's Lightning training_step, DataLoader collate and "
                                "metrics-recorder overheads; divided by the measured ratio it estimates the "
                                "reference loop on these cores")}
+    out = {"roofline": roofline, "rooflines": rooflines, "stages_us": {k: round(v, 3) for k, v in stage_us.items()},
+           "cpu_baseline": cpu}
+    if bf16_dev is not None:
+        out["bf16_vs_fp32"] = bf16_dev
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--workload", choices=tuple(WORKLOADS), default="C2",
+                    help="C2: CartPole-v1:ppo (the metric's config); C3: LunarLander-v3:ppo shapes (T=2048, B=64); "
+                         "C4/C5: ALE Pong/Breakout rgb_ppo (NatureCNN, Atari pixel pipeline)")
+    ap.add_argument("--env-dynamics", choices=("synthetic", "cartpole"), default="synthetic",
+                    help="MLP workloads: SURVEY §8d synthetic fixed-length episodes (default) or device CartPole-v1")
+    ap.add_argument("--n-envs", type=int, default=None, help="envs per GPU (weak scaling; default per workload)")
+    ap.add_argument("--no-graph", action="store_true", help="eager launches instead of the hipGraph")
+    ap.add_argument("--local-comm", action="store_true",
+                    help="N=1 only: run the multi-GPU chain through a one-rank communicator")
+    ap.add_argument("--comm", choices=("xgmi", "rccl"), default="xgmi",
+                    help="gradient-exchange transport for N>1 (and --local-comm): one-shot xGMI or RCCL")
+    ap.add_argument("--same-device", action="store_true",
+                    help="rehearsal on a one-GPU machine: all ranks share cuda:0 (gloo process group, "
+                         "xGMI exchange through same-device IPC); throughput is not meaningful")
+    ap.add_argument("--dtype", choices=("f32", "bf16"), default="f32",
+                    help="f32: the fp32 parity path (default, the metric's line); bf16: bf16 MFMA operands in the "
+                         "update (the MLP's fused chain, the NatureCNN's convolutions / GEMMs), reported as its own "
+                         "line with its deviation from fp32 over one whole update")
+    ap.add_argument("--dp-mode", choices=("local", "global"), default="local",
+                    help="N>1: local (each rank's own minibatches, gradients averaged: the default) or global (the "
+                         "reference's exact global minibatches split over the ranks, sums exchanged)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the line reports beside its headline figure: "
+                         "per-kernel stage times and rooflines, the exchange launch, the bf16 mode's deviation from "
+                         "fp32 (--dtype bf16) and the CPU baseline; a plain run times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (parameters, Adam moments, "
+                         "per-minibatch metrics, the rollout) as DIR/<name>.npy, float32; with --gpus above 1 "
+                         "rank 0's arrays only (its own rollout; the parameters are the same on every rank)")
+    ap.add_argument("--stage-reps", type=int, default=200, help="--full: launches per timed kernel stage")
+    ap.add_argument("--cpu-minibatches", type=int, default=-1,
+                    help="--full: minibatches timed in the CPU baseline (-1: the whole update, 0: no CPU baseline)")
+    args = ap.parse_args()
+    if args.gpus < 1:
+        ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        # no launcher around us: start one rank per GPU ourselves (before any GPU call)
+        sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world != args.gpus:
+        raise SystemExit(f"[bench] WORLD_SIZE={world} but --gpus {args.gpus}: they must agree")
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    dev_index = 0 if args.same_device else local_rank
+    torch.cuda.set_device(dev_index)
+    device = torch.device(f"cuda:{dev_index}")
+    if world > 1:
+        import torch.distributed as dist
+        if args.same_device:          # rehearsal: every rank on cuda:0, host-side process group
+            dist.init_process_group("gloo", rank=rank, world_size=world)
+        else:
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=device)
+
+    from gsamd.config import load_config
+    from gsamd.ppo_agent import DevicePPOAgent
+    torch.manual_seed(42)
+    env_id, variant, n_default = WORKLOADS[args.workload]
+    pixel = variant == "rgb_ppo"
+    n_envs = args.n_envs or n_default
+    # the benchmark's env is chosen explicitly: SURVEY §8d synthetic fixed-length episodes (or the
+    # synthetic Atari frame source), or the device CartPole-v1 dynamics
+    over = dict(n_envs=n_envs, env_dynamics="synthetic" if pixel else args.env_dynamics)
+    if args.dtype == "bf16":
+        over["precision"] = "bf16"
+    if args.dp_mode == "global":
+        over["dp_mode"] = "global"
+    cfg = load_config(env_id, variant, overrides=over)
+    agent = DevicePPOAgent(cfg, device=device, rank=rank, world_size=world,
+                           use_graph=not args.no_graph, track_stats=False)
+    comm = None
+    if world > 1 or args.local_comm:      # sized to this policy's flat gradient
+        from gsamd import distributed as gd
+        n_params = agent.policy_model.n_params
+        if world == 1:
+            comm = gd.init_local_comm(args.comm, n_params)
+        elif args.comm == "xgmi":
+            try:
+                # MLP: the in-backward exchange is checked on this job's shapes before the timed run
+                comm = gd.init_xgmi_comm(rank, world, n_params, device,
+                                         verify_shapes=None if pixel else (agent.policy_model.dims, cfg.batch_size,
+                                                                           int(agent.hparams().flags)))
+            except RuntimeError as e:     # every rank raises together: switch transport together
+                _log(f"[bench] {e}; using RCCL for the gradient exchange")
+                args.comm = "rccl (xgmi unavailable)"
+                comm = gd.init_device_comm(rank, world, device)
+        else:
+            comm = gd.init_device_comm(rank, world, device)
+        agent.comm = comm
+    comm_info = None
+    from gsamd.distributed import LAST_SELF_TEST as gd_self_test
+    if comm is not None:
+        from gsamd.distributed import comm_info as _comm_info
+        comm_info = _comm_info(comm)
+        if comm_info["nranks"] != world or comm_info["rank"] != rank:
+            raise RuntimeError(f"communicator reports {comm_info}, launcher says rank {rank} of {world}")
+    N, T = cfg.n_envs, cfg.n_steps
+
+    def barrier():
+        torch.cuda.synchronize()
+        if world > 1:
+            torch.distributed.barrier()
+        torch.cuda.synchronize()
+
+    if args.warmup < 2 and not args.no_graph:
+        _log("[bench] warning: --warmup < 2 times the rollout graph's capture (second collect)")
+    tw = time.perf_counter()
+    for _ in range(args.warmup):
+        agent.train_epoch()
+    barrier()
+    _log(f"[bench] rank {rank}: warmup {args.warmup} steps {time.perf_counter() - tw:.2f}s")
+    agent.phase_events = []
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        agent.train_epoch()
+    barrier()
+    elapsed = time.perf_counter() - t0
+    phases = agent.phase_events
+    agent.phase_events = None
+    collect_ms = sum(e[0].elapsed_time(e[1]) for e in phases) / len(phases)
+    update_ms = sum(e[1].elapsed_time(e[2]) for e in phases) / len(phases)
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if args.same_device else device)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        elapsed = float(t.item())
+    losses = agent.minibatch_losses()
+    if not (losses == losses).all():
+        raise RuntimeError("non-finite loss in the timed region")
+    total_env_steps = world * N * T * args.steps
+    value = total_env_steps / elapsed
+    ms_per_step = elapsed / args.steps * 1e3
+
+    if args.dump_outputs and rank == 0:      # before anything else touches the agent's state
+        dump_outputs(agent, args.dump_outputs)
+    in_bwd = None
+    if comm is not None and not pixel:
+        from gsamd.distributed import exchange_inside_bwd
+        in_bwd = exchange_inside_bwd(comm, agent.policy_model.dims, cfg.batch_size)
+    pm = agent.policy_model
+    extras = {}
+    if args.full:
+        extras = full_measurements(args, agent, cfg, comm, in_bwd, world, rank, device, barrier, update_ms)
 
     if comm is not None:       # a timed-out exchange never yields a bench line
         from gsamd.distributed import comm_status
@@ -667,15 +731,11 @@ def main():
                        # the rollout's step graph is captured on the second collect (the first runs
                        # eagerly and allocates): with --warmup < 2 the capture is inside the timed region
                        "rollout_graph_capture_in_timed_region": (not args.no_graph) and args.warmup < 2},
-            "roofline": roofline,
-            "rooflines": rooflines,
-            "stages_us": {k: round(v, 3) for k, v in stage_us.items()},
             "phases_ms": {"collect": round(collect_ms, 3), "update": round(update_ms, 3),
                           "update_us_per_minibatch": round(update_ms * 1e3 / agent.n_minibatches, 3)},
-            "cpu_baseline": cpu,
+            "full": bool(args.full),
         }
-        if bf16_dev is not None:
-            line["bf16_vs_fp32"] = bf16_dev
+        line.update(extras)      # --full: roofline, rooflines, stages_us, cpu_baseline (bf16_vs_fp32)
         print(json.dumps(line), flush=True)
     if comm is not None:
         from gsamd.distributed import destroy_comm

@@ -53,6 +53,41 @@ def test_launcher_propagates_a_rank_failure():
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
 
 
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every array of the last step as float32 .npy; one above the element cap is
+    written as the same seeded sample of its elements on every run."""
+    from types import SimpleNamespace as NS
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 64)
+    T, N = 4, 8
+    g = torch.Generator().manual_seed(0)
+    f = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+    buf = NS(obs=(torch.rand(T, N, 5, generator=g) * 255).to(torch.uint8), actions=torch.arange(T * N).reshape(T, N),
+             logprobs=f(T, N), values=f(T, N), rewards=f(T, N), dones=torch.zeros(T, N, dtype=torch.uint8),
+             advantages=f(T, N), returns=f(T, N), last_values=f(N))
+    agent = NS(policy_model=NS(params=f(40)), adam_m=f(40), adam_v=f(40), metrics_buf=f(3, 7),
+               get_rollout_collector=lambda stage: NS(buffer=buf))
+    bench.dump_outputs(agent, str(tmp_path / "a"))
+    bench.dump_outputs(agent, str(tmp_path / "b"))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == 13
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size <= 64 and np.array_equal(a, b), n
+    assert np.array_equal(np.load(tmp_path / "a" / "params.npy"), agent.policy_model.params.numpy())
+    assert np.array_equal(np.load(tmp_path / "a" / "rollout_actions.npy"), buf.actions.numpy().astype(np.float32))
+    obs = np.load(tmp_path / "a" / "rollout_obs.npy")          # 160 elements > 64: sampled
+    assert obs.shape == (64,) and set(obs.tolist()) <= set(buf.obs.reshape(-1).tolist())
+
+
+def test_bench_has_full_and_dump_outputs_options():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs" in r.stdout
+
+
 def test_bench_rejects_mismatched_world():
     env = dict(os.environ, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4"], capture_output=True,

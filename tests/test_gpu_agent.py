@@ -45,6 +45,38 @@ def test_checkpoint_round_trip(cuda, tmp_path, env, variant):
         assert torch.equal(t, sd[n])
 
 
+@pytest.mark.parametrize("env,variant", [("CartPole-v1", "ppo"), ("ALE-Pong-v5", "rgb_ppo")])
+def test_bench_dump_outputs_of_a_real_agent(cuda, tmp_path, monkeypatch, env, variant):
+    """bench.py --dump-outputs on the real agent and rollout buffer of both policy families: every
+    array is the float32 image of the device tensor it names; the frame stacks (u8, above the
+    element cap) come out as the seeded sample of their elements."""
+    import bench
+    a = _agent(cuda, env, variant)
+    a.train_epoch()
+    a.train_epoch()
+    torch.cuda.synchronize()
+    buf = a.get_rollout_collector("train").buffer
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1 << 16)
+    bench.dump_outputs(a, str(tmp_path))
+    want = {"params": a.policy_model.params, "adam_m": a.adam_m, "adam_v": a.adam_v,
+            "minibatch_metrics": a.metrics_buf, "rollout_obs": buf.obs, "rollout_actions": buf.actions,
+            "rollout_logprobs": buf.logprobs, "rollout_values": buf.values, "rollout_rewards": buf.rewards,
+            "rollout_dones": buf.dones, "rollout_advantages": buf.advantages, "rollout_returns": buf.returns,
+            "rollout_last_values": buf.last_values}
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(k + ".npy" for k in want)
+    for name, t in want.items():
+        got = np.load(tmp_path / (name + ".npy"))
+        ref = t.to(torch.float32).cpu().numpy()
+        assert got.dtype == np.float32 and np.isfinite(got).all(), name
+        if ref.size > 1 << 16:
+            pick = np.sort(np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(0, ref.size, 1 << 16))
+            ref = ref.reshape(-1)[pick]
+        assert got.shape == ref.shape and np.array_equal(got, ref), name
+    assert np.abs(np.load(tmp_path / "adam_v.npy")).max() > 0       # the update ran before the dump
+    sampled = [n for n, t in want.items() if t.numel() > 1 << 16]
+    assert ("rollout_obs" in sampled) == (variant == "rgb_ppo")
+
+
 def test_evaluate_episodes_keys_and_counts(cuda):
     a = _agent(cuda, episode_len=9)
     out = a.get_rollout_collector("val").evaluate_episodes(n_episodes=100, deterministic=True)

@@ -8,7 +8,7 @@ relative and the parameters after 8 lagged-Adam steps within 1e-4 relative L2 â€
 operands are exact in fp32, so what remains is the accumulation order and the odd bf16 rounding
 of an h1 / dh2 value the device and numpy compute 1 ulp apart; the device must also sit far
 closer to the bf16 emulation than to the fp32 oracle (the mode really rounds).  Against the fp32
-path: the mode's whole-update loss deviation bounded (the line bench.py --dtype bf16 reports)."""
+path: the mode's whole-update loss deviation bounded (the line bench.py --dtype bf16 --full reports)."""
 import numpy as np
 import pytest
 import torch

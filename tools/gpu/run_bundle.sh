@@ -18,9 +18,9 @@ if [ -n "$CNNK" ]; then
       -- python tools/cnn_kernel_run.py ${CNNK_ARGS} > $O/cnn_trace.log 2>&1 || exit 1
 fi
 [ -n "$C4B" ] || { rm -f $O/*/*kernel_trace.csv; exit 0; }
-step bench-c4 timeout -k 10 300 python bench.py --workload C4 --steps 2 --warmup 1 --cpu-minibatches 0 \
+step bench-c4 timeout -k 10 300 python bench.py --full --workload C4 --steps 2 --warmup 1 --cpu-minibatches 0 \
     > $O/bench_c4.json 2> $O/bench_c4.err && tail -c 600 $O/bench_c4.json || exit 1
-step bench-c4bf16 timeout -k 10 300 python bench.py --workload C4 --dtype bf16 --steps 2 --warmup 1 --cpu-minibatches 0 \
+step bench-c4bf16 timeout -k 10 300 python bench.py --full --workload C4 --dtype bf16 --steps 2 --warmup 1 --cpu-minibatches 0 \
     > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err && tail -c 600 $O/bench_c4_bf16.json || exit 1
 if [ -n "$AB" ]; then
   step ab timeout -k 10 600 bash tools/run_ab_bench.sh $AB > $O/ab.log 2>&1; rc=$?; cat $O/ab.log; [ $rc -eq 0 ] || exit $rc

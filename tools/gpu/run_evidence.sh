@@ -17,25 +17,25 @@ if on TESTS; then
   tail -3 $O/pytest.log
 fi
 if on BENCH; then
-  step bench timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err && tail -c 300 $O/bench.json || exit 1
+  step bench timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err && tail -c 300 $O/bench.json || exit 1
   step bench-rocprof timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/stats -o bench --output-format csv \
-      -- python bench.py --cpu-minibatches 0 > $O/bench_prof.log 2>&1 || exit 1
+      -- python bench.py --full --cpu-minibatches 0 > $O/bench_prof.log 2>&1 || exit 1
   step pmc-fetch timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -o pmc \
       -- python tools/pmc_run.py > $O/pmc_fetch.log 2>&1 &&
   step pmc-write timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_write -o pmc \
       -- python tools/pmc_run.py > $O/pmc_write.log 2>&1 || exit 1
 fi
 if on LINES; then
-  step bench-c2bf16 timeout -k 10 400 python bench.py --dtype bf16 --cpu-minibatches 0 \
+  step bench-c2bf16 timeout -k 10 400 python bench.py --full --dtype bf16 --cpu-minibatches 0 \
       > $O/bench_c2_bf16.json 2> $O/bench_c2_bf16.err && tail -c 300 $O/bench_c2_bf16.json || exit 1
   for w in C3 C4 C5; do
     # the CPU port's bounded sample: C3's full update is 327 680 minibatches (no CPU leg here, it
     # would outrun the box's silence watchdog); C4 / C5 time 8 vector steps + 3 minibatch steps
     cm=${CPU_MB:-0}; [ $w = C3 ] && cm=0
-    step bench-$w timeout -k 10 400 python bench.py --workload $w --steps 2 --warmup 1 --cpu-minibatches $cm \
+    step bench-$w timeout -k 10 400 python bench.py --full --workload $w --steps 2 --warmup 1 --cpu-minibatches $cm \
         > $O/bench_$w.json 2> $O/bench_$w.err && tail -c 300 $O/bench_$w.json || exit 1
   done
-  step bench-c4bf16 timeout -k 10 400 python bench.py --workload C4 --dtype bf16 --steps 2 --warmup 1 --cpu-minibatches 0 \
+  step bench-c4bf16 timeout -k 10 400 python bench.py --full --workload C4 --dtype bf16 --steps 2 --warmup 1 --cpu-minibatches 0 \
       > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err && tail -c 300 $O/bench_c4_bf16.json || exit 1
 fi
 if on CNNK; then
@@ -59,7 +59,7 @@ if on ATARI; then
   grep "env step" $O/atari.log
 fi
 if on SAME; then
-  step same2-global timeout -k 10 400 python bench.py --gpus 2 --same-device --workload C5 --dp-mode global --steps 2 \
+  step same2-global timeout -k 10 400 python bench.py --full --gpus 2 --same-device --workload C5 --dp-mode global --steps 2 \
       --warmup 1 --cpu-minibatches 0 > $O/bench_same2_global_c5.json 2> $O/bench_same2_global_c5.err &&
       tail -c 300 $O/bench_same2_global_c5.json || exit 1
 fi

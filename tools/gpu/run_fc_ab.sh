@@ -40,9 +40,9 @@ if [ -n "$STAMPS" ]; then
   grep -v "^W20" $O/stamps.log
 fi
 if [ -n "$C4B" ]; then
-  step bench-c4 timeout -k 10 300 python bench.py --workload C4 --steps 2 --warmup 1 --cpu-minibatches 0 \
+  step bench-c4 timeout -k 10 300 python bench.py --full --workload C4 --steps 2 --warmup 1 --cpu-minibatches 0 \
       > $O/bench_c4.json 2> $O/bench_c4.err && tail -c 400 $O/bench_c4.json || exit 1
-  step bench-c4bf16 timeout -k 10 300 python bench.py --workload C4 --dtype bf16 --steps 2 --warmup 1 --cpu-minibatches 0 \
+  step bench-c4bf16 timeout -k 10 300 python bench.py --full --workload C4 --dtype bf16 --steps 2 --warmup 1 --cpu-minibatches 0 \
       > $O/bench_c4_bf16.json 2> $O/bench_c4_bf16.err && tail -c 400 $O/bench_c4_bf16.json || exit 1
 fi
 if [ -n "$AB" ]; then

@@ -11,9 +11,9 @@ summ() { python -c "
 import json,sys
 for l in open(sys.argv[1]):
     if l.startswith('{'): d=json.loads(l); print(sys.argv[1], d['n_gpus'], d['value'], d['stages_us'], d['phases_ms'], d['config'].get('grad_exchange'))" "$1"; }
-timeout -k 10 300 python bench.py --local-comm --steps 3 --warmup 1 --cpu-minibatches 0 \
+timeout -k 10 300 python bench.py --full --local-comm --steps 3 --warmup 1 --cpu-minibatches 0 \
     > gpurun_out/mg/bench_localcomm.json 2> gpurun_out/mg/bench_localcomm.err && summ gpurun_out/mg/bench_localcomm.json &&
-timeout -k 10 300 python bench.py --gpus 2 --same-device --steps 2 --warmup 1 --cpu-minibatches 0 \
+timeout -k 10 300 python bench.py --full --gpus 2 --same-device --steps 2 --warmup 1 --cpu-minibatches 0 \
     > gpurun_out/mg/bench_same2.json 2> gpurun_out/mg/bench_same2.err && summ gpurun_out/mg/bench_same2.json &&
-timeout -k 10 300 python bench.py --gpus 4 --same-device --steps 2 --warmup 1 --cpu-minibatches 0 \
+timeout -k 10 300 python bench.py --full --gpus 4 --same-device --steps 2 --warmup 1 --cpu-minibatches 0 \
     > gpurun_out/mg/bench_same4.json 2> gpurun_out/mg/bench_same4.err && summ gpurun_out/mg/bench_same4.json

@@ -7,6 +7,7 @@ timeout -k 10 600 python -u -m pytest ${SEL:-tests/test_gpu_lagged.py tests/test
 tail -1 gpurun_out/q/pytest.log
 timeout -k 10 200 python tools/stamp_run.py ${STAMP_MODE:---spans} > gpurun_out/q/stamps.log 2>&1 || exit 1
 grep -v amdgpu.ids gpurun_out/q/stamps.log
+BENCH_ARGS="--full ${BENCH_ARGS}"     # the summary below reads the line's stages_us
 timeout -k 10 300 python bench.py --cpu-minibatches 0 ${BENCH_ARGS} > gpurun_out/q/bench.json 2> gpurun_out/q/bench.err || exit 1
 python -c "
 import json

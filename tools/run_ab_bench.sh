@@ -4,6 +4,7 @@
 # does not enter the comparison).  Usage: run_ab_bench.sh NAME [NAME ...]
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/abb
+BENCH_ARGS="--full ${BENCH_ARGS}"     # the summary below reads the line's stages_us
 for i in 1 2 3; do
   for v in intree "$@"; do
     if [ "$v" = intree ]; then lib=""; else lib="ab_libs/libgsamd_$v.so"; [ -f "$lib" ] || lib="tools/libgsamd_$v.so"; fi
