@@ -21,6 +21,13 @@ ARCH = "gfx950"
 # with the reference's numpy float32 loop)
 EXTRA = {"gs_gae.hip": ["-ffp-contract=off"], "gs_mlp.hip": ["-ffp-contract=off"], "gs_atari.hip": ["-ffp-contract=off"],
          "gs_cartpole.hip": ["-ffp-contract=off"]}
+# Kernel-argument preload: the leading 14 dwords of a kernel's plain (non-struct) arguments arrive
+# in SGPRs with the wave, so the update chain's entries (k_fwd_chain / k_bwd_chain, whose argument
+# lists are ordered for it) issue their first load burst without a scalar memory round trip.
+# GSAMD_KERNARG_PRELOAD=0 builds without it (the A/B arm of DESIGN.md §4.1).
+KERNARG_PRELOAD = os.environ.get("GSAMD_KERNARG_PRELOAD", "1") != "0"
+if KERNARG_PRELOAD:
+    EXTRA["gs_mlp.hip"] = EXTRA["gs_mlp.hip"] + ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
 
 
 def _sources():
@@ -59,15 +66,22 @@ def _compile(src, build_dir=None, defines=(), csrc=None, hashes=None):
                 os.remove(obj)
             with open(stamp, "w") as f:
                 f.write(" ".join(hdefs))
-    if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(d) for d in deps):
-        return None
     cmd = [HIPCC, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-c", path, "-o", obj]
     if src.endswith(".hip"):
         cmd[1:1] = [f"--offload-arch={ARCH}", "-x", "hip"]
     cmd += EXTRA.get(src, []) + [f"-D{d}" for d in defines] + hdefs
+    # an object built with other per-file flags (GSAMD_KERNARG_PRELOAD toggled) is stale
+    flags = obj + ".flags"
+    want = " ".join(EXTRA.get(src, []))
+    if os.path.exists(obj) and (not os.path.exists(flags) or open(flags).read() != want):
+        os.remove(obj)
+    if os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(d) for d in deps):
+        return None
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError(f"compile failed: {' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+    with open(flags, "w") as f:
+        f.write(want)
     return src
 
 

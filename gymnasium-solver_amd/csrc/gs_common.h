@@ -22,6 +22,7 @@ extern __device__ unsigned long long g_stamp_cnt[8];
 #define GS_STAMP_BEGIN_IF(k, cond)                                                 \
     unsigned long long _st_t[17];                                                  \
     int _st_n = 0;                                                                 \
+    unsigned long long _st_entry = 0;                                              \
     const bool _st_on = (cond) && threadIdx.x == 0;                                \
     const int _st_k = (k);                                                         \
     if (_st_on) _st_t[0] = __builtin_amdgcn_s_memtime();
@@ -29,15 +30,23 @@ extern __device__ unsigned long long g_stamp_cnt[8];
 #define GS_STAMP(i)                                                                \
     if (_st_on) _st_t[(i) + 1] = __builtin_amdgcn_s_memtime();                     \
     _st_n = (i) + 1;
+// kernel entry -> the point where the first vector load is issued (behind every scalar wait for
+// the kernel arguments): column 15 of the slot, beside its phases
+#define GS_STAMP_T0 const unsigned long long _st_t0 = __builtin_amdgcn_s_memtime();
+#define GS_STAMP_ENTRY                                                             \
+    if (_st_on) _st_entry = __builtin_amdgcn_s_memtime() - _st_t0;
 #define GS_STAMP_END(i)                                                            \
     GS_STAMP(i)                                                                    \
     if (_st_on) {                                                                  \
+        atomicAdd(&g_stamp_acc[_st_k][15], _st_entry);                             \
         for (int _j = 0; _j < _st_n; ++_j)                                         \
             atomicAdd(&g_stamp_acc[_st_k][_j], _st_t[_j + 1] - _st_t[_j]);         \
         atomicAdd(&g_stamp_cnt[_st_k], 1ull);                                      \
     }
 #else
 #define GS_STAMP_BEGIN(k)
+#define GS_STAMP_T0
+#define GS_STAMP_ENTRY
 #define GS_STAMP_BEGIN_IF(k, cond)
 #define GS_STAMP(i)
 #define GS_STAMP_END(i)

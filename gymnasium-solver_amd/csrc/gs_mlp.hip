@@ -292,16 +292,24 @@ static_assert(kFwdAdamThreads == 256 || kFwdAdamThreads == 512, "lagged forward:
 // rows (FusedFwd::act, kActRec words): dead counts of the 16 h1 columns of chunk cb and of its 16 h2
 // columns and the float sums of z and z^2 of both (the pre-activation values of the forward hooks on
 // backbone.0 / backbone.2, utils/models.py:121-147), on the block's last wave after the h2 epilogue
-template <class S, bool FUSED, bool ADAM = false, bool STATS = false>
-__global__ __launch_bounds__(ADAM ? kFwdAdamThreads : 256) void k_fwd_hidden(
-    const float *__restrict__ P, Layout Lrt, const float *__restrict__ obs, const int32_t *__restrict__ idx, int T,
-    int N, int rows, float *__restrict__ x_out, float *__restrict__ h1_out, float *__restrict__ h2_out,
-    float *__restrict__ zpart, float *__restrict__ obs_copy, const int32_t *__restrict__ stop, RowGather rg,
-    FusedFwd ff, LossArgs la, uint16_t *__restrict__ h2mask, AdamFwd af = AdamFwd{})
+//
+// One body, two entries: k_fwd_hidden (the unfused single-step kernels: runtime shapes, index
+// stream, stop flag) and k_fwd_chain (the fused update chain, below).  BASE: a chunked graph
+// replay, whose step index is k_local + the chunk's device step base; without it (eager steps and
+// a whole-update capture) the body neither tests nor reads FusedFwd::step_base.  The fused chain
+// has no stop flag (no KL early stop), so a FUSED body never loads one.
+template <class S, bool FUSED, bool ADAM, bool STATS, bool BASE>
+__device__ __forceinline__ void fwd_hidden_body(
+    const float *__restrict__ P, const Layout &Lrt, const float *__restrict__ obs, const int32_t *__restrict__ idx,
+    int T, int N, int rows, float *__restrict__ x_out, float *__restrict__ h1_out, float *__restrict__ h2_out,
+    float *__restrict__ zpart, float *__restrict__ obs_copy, const int32_t *__restrict__ stop, const RowGather &rg,
+    const FusedFwd &ff, uint16_t *__restrict__ h2mask, const AdamFwd &af)
 {
     GS_STAMP_BEGIN(0)
     GS_SPAN_T0
-    if (stop && *stop) return;
+    GS_STAMP_T0
+    if constexpr (!FUSED)
+        if (stop && *stop) return;
     extern __shared__ float lds[];
     const Layout L = S::lay(Lrt);
     const int D = L.D, H1 = L.H1, H2 = L.H2, A1 = L.A + 1;
@@ -322,8 +330,10 @@ __global__ __launch_bounds__(ADAM ? kFwdAdamThreads : 256) void k_fwd_hidden(
     float *red = h1s + kTile * ldh;
     float *h2s = red + 1024;
 
-    if (rg.step_base && idx) idx += *rg.step_base * rows;
-    const int64_t kstep = FUSED ? ff.k_local + (ff.step_base ? *ff.step_base : 0) : 0;
+    if constexpr (!FUSED)
+        if (rg.step_base && idx) idx += *rg.step_base * rows;
+    int64_t kstep = FUSED ? ff.k_local : 0;
+    if constexpr (FUSED && BASE) kstep += ff.step_base ? *ff.step_base : 0;
     if constexpr (ADAM) GS_SPAN_START(0, kstep)
     // ---- phase 0: every operand of this workgroup, all loads in flight together.
     //      Threads 0..15 run the dependent idx -> row -> obs/fields chain while the rest
@@ -384,6 +394,7 @@ __global__ __launch_bounds__(ADAM ? kFwdAdamThreads : 256) void k_fwd_hidden(
         float sl[NS];     // slots past n_slots and the non-norm lanes are dropped in the norm
 #pragma unroll
         for (int j = 0; j < NS; ++j) sl[j] = ld1(af.sumsq, nrm ? min(tid + 256 * j, aa.n_slots - 1) : 0);
+        GS_STAMP_ENTRY
         float4 w1p[NQP], w1m[NQP], w1v[NQP], t[NQ][NRB];  // W1|b1 (param order), dW1|db1 partials
         const float *tsrc = fold ? af.part1 : af.G;
         const int64_t tstride = fold ? (int64_t)n1 : 0;
@@ -883,6 +894,60 @@ __global__ __launch_bounds__(ADAM ? kFwdAdamThreads : 256) void k_fwd_hidden(
     if constexpr (ADAM) GS_SPAN_END(0, kstep)
 }
 
+template <class S, bool FUSED>
+__global__ __launch_bounds__(256) void k_fwd_hidden(
+    const float *__restrict__ P, Layout Lrt, const float *__restrict__ obs, const int32_t *__restrict__ idx, int T,
+    int N, int rows, float *__restrict__ x_out, float *__restrict__ h1_out, float *__restrict__ h2_out,
+    float *__restrict__ zpart, float *__restrict__ obs_copy, const int32_t *__restrict__ stop, RowGather rg,
+    uint16_t *__restrict__ h2mask)
+{
+    static_assert(!FUSED, "the fused chain's forward enters through k_fwd_chain");
+    fwd_hidden_body<S, false, false, false, false>(P, Lrt, obs, idx, T, N, rows, x_out, h1_out, h2_out, zpart,
+                                                   obs_copy, stop, rg, FusedFwd{}, h2mask, AdamFwd{});
+}
+
+// The fused chain's forward entry.  Every kernel node of a captured update reads its own argument
+// block once per replay, so the block is never cached when the kernel starts and each dependent
+// scalar load of it is a full memory round trip ahead of the first operand load.  The entry is
+// therefore lean and ordered: the leading arguments are plain pointers and ints (a by-value struct
+// ends the prefix the hardware can preload into SGPRs: 14 dwords), in the issue order of the
+// lagged forward's first load burst; store targets and hyper-parameters follow in FwdTail.  The
+// compile-time shape carries the layout and the batch, so none of them is passed.
+struct FwdTail {
+    const float *xg;                   // FusedFwd::xg
+    const int64_t *step_base;          // BASE only
+    float *x_out, *h1_out, *h2_out, *zpart;
+    uint16_t *h2mask;
+    float *Pout, *Mout, *Vout;         // AdamFwd's store targets
+    float *metrics;
+    double *normsq;
+    const float *sched;
+    uint32_t *act;                     // STATS only
+    float max_norm, one_minus_b1, b2, one_minus_b2, neg_step_size, inv_bc2_sqrt, eps, grad_scale;
+    int force;
+};
+template <class S, bool ADAM, bool STATS, bool BASE>
+__global__ __launch_bounds__(ADAM ? kFwdAdamThreads : 256) void k_fwd_chain(
+    const float *__restrict__ sumsq, const float *__restrict__ part1, const float *__restrict__ P,
+    const float *__restrict__ Min, const float *__restrict__ Vin, const float *__restrict__ G, int n_slots,
+    int k_local, FwdTail t)
+{
+    static_assert(S::Bc > 0 && S::H1c > 0, "chain entry: compile-time shapes only");
+    FusedFwd ff{};
+    ff.xg = t.xg, ff.step_base = t.step_base, ff.k_local = k_local, ff.act = t.act;
+    AdamFwd af{};
+    if constexpr (ADAM) {
+        af.Min = Min, af.Vin = Vin, af.G = G, af.part1 = part1, af.sumsq = sumsq;
+        af.Pout = t.Pout, af.Mout = t.Mout, af.Vout = t.Vout, af.metrics = t.metrics, af.force = t.force;
+        af.aa.max_norm = t.max_norm, af.aa.one_minus_b1 = t.one_minus_b1, af.aa.b2 = t.b2;
+        af.aa.one_minus_b2 = t.one_minus_b2, af.aa.neg_step_size = t.neg_step_size;
+        af.aa.inv_bc2_sqrt = t.inv_bc2_sqrt, af.aa.eps = t.eps, af.aa.grad_scale = t.grad_scale;
+        af.aa.n_slots = n_slots, af.aa.sched = t.sched, af.aa.normsq = t.normsq;
+    }
+    fwd_hidden_body<S, true, ADAM, STATS, BASE>(P, Layout{}, nullptr, nullptr, 0, 0, S::Bc, t.x_out, t.h1_out, t.h2_out,
+                                                t.zpart, nullptr, nullptr, RowGather{}, ff, t.h2mask, af);
+}
+
 static int set_lds_limit(const void *fn, size_t bytes);
 template <class F>
 static int with_shape(const Layout &L, int64_t B, F &&f);
@@ -901,7 +966,7 @@ int launch_fwd_hidden(const float *params, const Layout &L, const float *obs, co
         if (rc) return rc;
         hipLaunchKernelGGL((k_fwd_hidden<Sh, false>), grid, dim3(256), fwd_lds_bytes(L), s, params, L, obs, idx,
                            (int)T, (int)N, (int)rows, x_out, h1_out, h2_out, zpart, obs_copy, stop_flag, g,
-                           FusedFwd{}, LossArgs{}, h2_out ? h2mask : (uint16_t *)nullptr);
+                           h2_out ? h2mask : (uint16_t *)nullptr);
         GS_LAUNCH_CHECK("k_fwd_hidden");
         return GS_OK;
     });
@@ -1676,25 +1741,32 @@ __device__ __forceinline__ void store_metric_groups(const double *dscr, int n, i
     }
 }
 
-template <class S, bool FUSED>
-__global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout Lrt, int Brt,
-                                             const float *__restrict__ x, const float *__restrict__ h1,
-                                             const float *__restrict__ h2, const float *__restrict__ dz,
-                                             float *__restrict__ G, float *__restrict__ part1,
-                                             float *__restrict__ sumsq, const int32_t *__restrict__ stop,
-                                             const float *__restrict__ zpart, FusedFwd ff, LossArgs la,
-                                             const uint16_t *__restrict__ h2mask, BwdXchg bx)
+// One body, two entries (as the forward): k_bwd (unfused steps, and the fused chain with the
+// in-backward xGMI exchange) and k_bwd_chain (the single-GPU fused chain, below).  XCHG: the entry
+// carries a BwdXchg; BASE: a chunked graph replay (k_local + the chunk's device step base).  A
+// FUSED body never loads a stop flag.
+template <class S, bool FUSED, bool XCHG, bool BASE>
+__device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layout &Lrt, int Brt,
+                                         const float *__restrict__ x, const float *__restrict__ h1,
+                                         const float *__restrict__ h2, const float *__restrict__ dz,
+                                         float *__restrict__ G, float *__restrict__ part1,
+                                         float *__restrict__ sumsq, const int32_t *__restrict__ stop,
+                                         const float *__restrict__ zpart, const FusedFwd &ff, const LossArgs &la,
+                                         const uint16_t *__restrict__ h2mask, const BwdXchg &bx)
 {
     GS_SPAN_T0
-    if (stop && *stop) return;
+    GS_STAMP_T0
+    if constexpr (!FUSED)
+        if (stop && *stop) return;
     // multi-GPU: every output value goes through bwd_exchange before it is stored (its
     // counter is read here, off the epilogue's critical path)
-    const bool xchg = bx.world > 1;
+    const bool xchg = XCHG && bx.world > 1;
     const uint32_t xseq = xchg ? bx.seq[blockIdx.x] + 1u : 0u;
     // this minibatch's index in the update (graph replay: + the chunk's device step base), read
     // once here: a later re-read (the metric-group stores come after LDS/global stores the
     // compiler cannot order it against) would be a dependent round trip in the middle of a phase
-    const int64_t kstep = FUSED ? ff.k_local + (ff.step_base ? *ff.step_base : 0) : 0;
+    int64_t kstep = FUSED ? ff.k_local : 0;
+    if constexpr (FUSED && BASE) kstep += ff.step_base ? *ff.step_base : 0;
     if constexpr (FUSED) GS_SPAN_START(1, kstep)
     extern __shared__ float lds[];
     __shared__ float sbuf[FUSED ? 3 * 272 : 272];    // fused: role C's {slot, policy, value} sums
@@ -1744,6 +1816,7 @@ __global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout
                 const int b = tid + 256 * j;
                 mr[j] = (int)h2mask[(int64_t)min(b, cB - 1) * cncb + nb];
             }
+            GS_STAMP_ENTRY
 #pragma unroll
             for (int j = 0; j < NH1; ++j) {
                 const int u = tid + 256 * j, b = u / cq, c4 = u % cq;
@@ -2013,6 +2086,7 @@ __global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout
                     const int u = min(tid + j * kLd, kRowsB * cncb - 1), i = u / cncb, c = u - i * cncb;
                     mr[j] = (int)h2mask[(int64_t)min(b0 + i, cB - 1) * cncb + c];
                 }
+                GS_STAMP_ENTRY
 #pragma unroll
                 for (int j = 0; j < NW; ++j) {
                     const int u = tid + j * kLd, n = min(u >> 2, cH2 - 1), c4 = u & 3;
@@ -2097,18 +2171,21 @@ __global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout
             atomicAdd(&g_stamp_cnt[6], 1ull);
         }
 #endif
-        if constexpr (FUSED)      // the kb == 0 slab also keeps its rows' metric sums
+        if constexpr (FUSED) {    // the kb == 0 slab also keeps its rows' metric sums
             loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, b0, kRowsB, dzs, nullptr, kLd, 256 - kLd);
+        } else {
+            for (int u = tid; u < kRowsB * A1; u += 256)
+                dzs[u] = b0 * A1 + u < B * A1 ? dz[(int64_t)b0 * A1 + u] : 0.0f;
+        }
 #ifdef GS_STAMPS
+        // (behind the braces above: an unbraced `else` after this block bound to its `if`, and the
+        // stamp build's fused role B then also read dz, which the chain entry does not pass)
         if (bid == 0 && tid == 192) {   // loss wave: its rows' loss + gradient
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             atomicAdd(&g_stamp_acc[7][0], __builtin_amdgcn_s_memtime() - t_rb0);
             atomicAdd(&g_stamp_cnt[7], 1ull);
         }
 #endif
-        else
-            for (int u = tid; u < kRowsB * A1; u += 256)
-                dzs[u] = b0 * A1 + u < B * A1 ? dz[(int64_t)b0 * A1 + u] : 0.0f;
         __syncthreads();
         GS_STAMP(0)
         // 32 rows = 2 row tiles; waves (0,1) / (2,3) split K = H2 of tile 0 / 1 in halves; 64 rows =
@@ -2367,6 +2444,7 @@ __global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout
                 hr[j] = *reinterpret_cast<const float4 *>(h2 + (int64_t)min(b, cB - 1) * Lc.H2 +
                                                           min(n0 + 4 * c4, Lc.H2 - 4));
             }
+            GS_STAMP_ENTRY
             loss_in();
 #pragma unroll
             for (int j = 0; j < NH; ++j) {
@@ -2522,6 +2600,46 @@ __global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout
         GS_STAMP_END(1)
         if constexpr (FUSED) GS_SPAN_END(1, kstep)
     }
+}
+
+template <class S, bool FUSED>
+__global__ __launch_bounds__(256) void k_bwd(const float *__restrict__ P, Layout Lrt, int Brt,
+                                             const float *__restrict__ x, const float *__restrict__ h1,
+                                             const float *__restrict__ h2, const float *__restrict__ dz,
+                                             float *__restrict__ G, float *__restrict__ part1,
+                                             float *__restrict__ sumsq, const int32_t *__restrict__ stop,
+                                             const float *__restrict__ zpart, FusedFwd ff, LossArgs la,
+                                             const uint16_t *__restrict__ h2mask, BwdXchg bx)
+{
+    bwd_body<S, FUSED, true, true>(P, Lrt, Brt, x, h1, h2, dz, G, part1, sumsq, stop, zpart, ff, la, h2mask, bx);
+}
+
+// The single-GPU fused chain's backward entry (see k_fwd_chain): the leading arguments are the 14
+// preloadable dwords, the operands of the three roles' first load bursts.  The per-update field
+// arrays fa | folp | fov | fadv | fret lie at one stride (carve_fused), so one base pointer and the
+// stride stand for five pointers.  h2 (role C's tile) no longer fits the prefix and leads the tail.
+struct BwdTail {
+    const float *h2;
+    float *G, *part1, *sumsq;
+    double *mpart;
+    float *headsq;
+    const int64_t *step_base;          // BASE only
+    LossArgs la;
+};
+template <class S, bool BASE>
+__global__ __launch_bounds__(256) void k_bwd_chain(const float *__restrict__ P, const float *__restrict__ h1,
+                                                   const uint16_t *__restrict__ h2mask,
+                                                   const float *__restrict__ zpart, const float *__restrict__ fields,
+                                                   const float *__restrict__ x, int fstride, int k_local, BwdTail t)
+{
+    static_assert(S::Bc > 0 && S::H1c > 0, "chain entry: compile-time shapes only");
+    FusedFwd ff{};
+    ff.fa = reinterpret_cast<const int32_t *>(fields);
+    ff.folp = fields + fstride, ff.fov = fields + 2 * (int64_t)fstride;
+    ff.fadv = fields + 3 * (int64_t)fstride, ff.fret = fields + 4 * (int64_t)fstride;
+    ff.mpart = t.mpart, ff.headsq = t.headsq, ff.step_base = t.step_base, ff.k_local = k_local;
+    bwd_body<S, true, false, BASE>(P, Layout{}, S::Bc, x, h1, t.h2, nullptr, t.G, t.part1, t.sumsq, nullptr, zpart, ff,
+                                   t.la, h2mask, BwdXchg{});
 }
 
 // ------------------------------------------------------------------------------------
@@ -2809,6 +2927,10 @@ static int set_lds_limit(const void *fn, size_t bytes)
     return GS_OK;
 }
 
+// the fused chain's lean entries (k_fwd_chain / k_bwd_chain) exist for the compile-time shapes
+template <class Sh>
+constexpr bool chain_shape() { return Sh::AEX > 0 && Sh::H1c > 0 && Sh::Bc > 0; }
+
 // the bf16 mode's instantiations: compile-time shapes whose backward forms dh2 in registers
 // (the fast role-A / role-B paths carry the bf16 operand pairs)
 template <class Sh>
@@ -2849,7 +2971,18 @@ int prepare_kernels(const Layout &L, int64_t B)
     if (rc) return rc;
     if (has_fused(L, B)) {
         rc = with_shape(L, B, [&](auto sh) {
-            return set_lds_limit((const void *)k_bwd<decltype(sh), true>, bwd_lds_bytes(L, B));
+            using Sh = decltype(sh);
+            const size_t lds = bwd_lds_bytes(L, B);
+            int r = set_lds_limit((const void *)k_bwd<Sh, true>, lds);
+            if constexpr (chain_shape<Sh>()) {
+                if (!r) r = set_lds_limit((const void *)k_bwd_chain<Sh, false>, lds);
+                if (!r) r = set_lds_limit((const void *)k_bwd_chain<Sh, true>, lds);
+                if constexpr (bf16_shape<Sh>()) {
+                    if (!r) r = set_lds_limit((const void *)k_bwd_chain<Bf16Shape<Sh>, false>, lds);
+                    if (!r) r = set_lds_limit((const void *)k_bwd_chain<Bf16Shape<Sh>, true>, lds);
+                }
+            }
+            return r;
         });
         if (rc) return rc;
     }
@@ -2858,9 +2991,10 @@ int prepare_kernels(const Layout &L, int64_t B)
     });
     if (rc) return rc;
     if (!has_fused(L, B)) return GS_OK;
-    return with_shape(L, B, [&](auto sh) {
-        return set_lds_limit((const void *)k_fwd_hidden<decltype(sh), true>, fwd_lds_bytes(L));
-    });
+    // the fused chain's forward entries (k_fwd_chain) run compile-time shapes whose LDS stays under
+    // the default limit
+    GS_REQUIRE(fwd_lds_bytes(L) <= 65536, "fused forward: %zu bytes of LDS exceed the default limit", fwd_lds_bytes(L));
+    return GS_OK;
 }
 
 int launch_heads_act(const float *P, const Layout &L, const float *zpart, int64_t rows, int mode, uint64_t seed,
@@ -2925,10 +3059,40 @@ int launch_bwd(const float *P, const Layout &L, int64_t B, const Workspace &ws, 
                    nblk);
         bx = *bxp;
     }
+    GS_REQUIRE(!ff || !stop, "the fused chain takes no stop flag (it runs only without a KL early stop)");
+    GS_REQUIRE(!ff || la, "fused backward: no loss arguments");
+    const bool lean = ff && bx.world <= 1;      // the single-GPU chain entry (k_bwd_chain)
+    BwdTail t{};
+    int64_t fstride = 0;
+    if (lean) {
+        fstride = ff->folp - reinterpret_cast<const float *>(ff->fa);
+        GS_REQUIRE(fstride > 0 && fstride < ((int64_t)1 << 29) && ff->fov == ff->folp + fstride &&
+                       ff->fadv == ff->fov + fstride && ff->fret == ff->fadv + fstride,
+                   "fused backward: the per-update field arrays are not at one stride");
+        t.h2 = ws.h2, t.G = G, t.part1 = ws.part1, t.sumsq = ws.sumsq;
+        t.mpart = ff->mpart, t.headsq = ff->headsq, t.step_base = ff->step_base, t.la = *la;
+    }
     return with_shape(L, B, [&](auto sh) {
         using Sh = decltype(sh);
-        if (ff && la && la->bf16) {      // the bf16 mode (GS_HP_BF16)
+        // the single-GPU fused chain: S = the shape with fp32 or bf16 operands
+        auto chain = [&](auto shape) -> int {
+            using S = decltype(shape);
+            const float *fields = reinterpret_cast<const float *>(ff->fa);
+            const void *fn = ff->step_base ? (const void *)k_bwd_chain<S, true> : (const void *)k_bwd_chain<S, false>;
+            int rc = set_lds_limit(fn, lds);
+            if (rc) return rc;
+            if (ff->step_base)
+                hipLaunchKernelGGL((k_bwd_chain<S, true>), dim3(nblk), dim3(256), lds, s, P, ws.h1, ws.h2mask, ws.zpart,
+                                   fields, ws.x, (int)fstride, ff->k_local, t);
+            else
+                hipLaunchKernelGGL((k_bwd_chain<S, false>), dim3(nblk), dim3(256), lds, s, P, ws.h1, ws.h2mask,
+                                   ws.zpart, fields, ws.x, (int)fstride, ff->k_local, t);
+            GS_LAUNCH_CHECK("k_bwd_chain");
+            return GS_OK;
+        };
+        if (ff && la->bf16) {      // the bf16 mode (GS_HP_BF16)
             if constexpr (bf16_shape<Sh>()) {
+                if (lean) return chain(Bf16Shape<Sh>{});
                 int rc = set_lds_limit((const void *)k_bwd<Bf16Shape<Sh>, true>, lds);
                 if (rc) return rc;
                 hipLaunchKernelGGL((k_bwd<Bf16Shape<Sh>, true>), dim3(nblk), dim3(256), lds, s, P, L, (int)B, ws.x,
@@ -2939,7 +3103,14 @@ int launch_bwd(const float *P, const Layout &L, int64_t B, const Workspace &ws, 
                 GS_REQUIRE(false, "precision bf16: no bf16 instantiation of the MLP chain for this shape");
             }
         }
-        if (ff) {
+        if (lean) {
+            if constexpr (chain_shape<Sh>()) {
+                return chain(sh);
+            } else {
+                GS_REQUIRE(false, "fused backward: no compile-time instantiation for this shape");
+            }
+        }
+        if (ff) {      // the fused chain with the exchange inside the backward (xGMI)
             int rc = set_lds_limit((const void *)k_bwd<Sh, true>, lds);
             if (rc) return rc;
             hipLaunchKernelGGL((k_bwd<Sh, true>), dim3(nblk), dim3(256), lds, s, P, L, (int)B, ws.x, ws.h1, ws.h2,
@@ -3471,53 +3642,60 @@ int launch_fwd_fused(const float *params, const Layout &L, int64_t B, const Fuse
     // GS_HP_ACT_STATS (ff.act): the STATS instantiations, whose epilogue records the activation
     // statistics (compile-time shapes with D <= 8 and at most one h1 chunk per column block)
     GS_REQUIRE(!ff.act || (L.D <= 8 && L.H1 <= L.H2), "activation statistics in the fused forward: D <= 8, H1 <= H2");
+    GS_REQUIRE(!stop, "the fused chain takes no stop flag (it runs only without a KL early stop)");
+    GS_REQUIRE(!af || ((af->part1 ? af->aa.nrb > 0 : af->aa.nrb == 0) && af->aa.n_slots <= 512),
+               "lagged Adam: bad slot / partial counts");
+    FwdTail t{};
+    t.xg = ff.xg, t.step_base = ff.step_base, t.act = ff.act;
+    t.x_out = ws.x, t.h1_out = ws.h1, t.h2_out = ws.h2, t.zpart = ws.zpart, t.h2mask = ws.h2mask;
+    const AdamFwd a = af ? *af : AdamFwd{};
+    t.Pout = a.Pout, t.Mout = a.Mout, t.Vout = a.Vout, t.metrics = a.metrics, t.normsq = a.aa.normsq;
+    t.sched = a.aa.sched, t.force = a.force;
+    t.max_norm = a.aa.max_norm, t.one_minus_b1 = a.aa.one_minus_b1, t.b2 = a.aa.b2, t.one_minus_b2 = a.aa.one_minus_b2;
+    t.neg_step_size = a.aa.neg_step_size, t.inv_bc2_sqrt = a.aa.inv_bc2_sqrt, t.eps = a.aa.eps;
+    t.grad_scale = a.aa.grad_scale;
+    const int k_local = ff.k_local;
     return with_shape(L, B, [&](auto sh) {
         using Sh = decltype(sh);
-        auto go = [&](auto stats) -> int {
-            constexpr bool ST = decltype(stats)::value && (Sh::H1c > 0);
-            const float *no_obs = nullptr;
-            const int32_t *no_idx = nullptr;
-            float *no_copy = nullptr;
+        if constexpr (!chain_shape<Sh>()) {
+            GS_REQUIRE(false, "fused forward: no compile-time instantiation for this shape");
+        } else {
+            // S: the shape (fp32 or bf16 operands); stats / base: the STATS and BASE instantiations
+            auto go = [&](auto shape, auto stats, auto base) -> int {
+                using S = decltype(shape);
+                constexpr bool ST = decltype(stats)::value, BS = decltype(base)::value;
+                if (af) {   // forward carrying the previous minibatch's clip + Adam (dW1|db1 partials)
+                    if constexpr (lagged_shape<Sh>()) {
+                        hipLaunchKernelGGL((k_fwd_chain<S, true, ST, BS>), grid, dim3(kFwdAdamThreads),
+                                           fwd_lds_bytes(L), s, a.sumsq, a.part1, params, a.Min, a.Vin, a.G,
+                                           a.aa.n_slots, k_local, t);
+                        GS_LAUNCH_CHECK("k_fwd_chain<adam>");
+                        return GS_OK;
+                    } else {
+                        GS_REQUIRE(false, "lagged Adam: no compile-time instantiation for this shape");
+                    }
+                }
+                const float *none = nullptr;
+                hipLaunchKernelGGL((k_fwd_chain<S, false, ST, BS>), grid, dim3(256), fwd_lds_bytes(L), s, none, none,
+                                   params, none, none, none, 0, k_local, t);
+                GS_LAUNCH_CHECK("k_fwd_chain");
+                return GS_OK;
+            };
+            auto go_sb = [&](auto shape) -> int {
+                if (ff.act) return ff.step_base ? go(shape, std::true_type{}, std::true_type{})
+                                                : go(shape, std::true_type{}, std::false_type{});
+                return ff.step_base ? go(shape, std::false_type{}, std::true_type{})
+                                    : go(shape, std::false_type{}, std::false_type{});
+            };
             if (la.bf16) {      // the bf16 mode (GS_HP_BF16)
                 if constexpr (bf16_shape<Sh>() && lagged_shape<Sh>()) {
-                    using Sb = Bf16Shape<Sh>;
-                    if (af) {
-                        GS_REQUIRE((af->part1 ? af->aa.nrb > 0 : af->aa.nrb == 0) && af->aa.n_slots <= 512,
-                                   "lagged Adam: bad slot / partial counts");
-                        hipLaunchKernelGGL((k_fwd_hidden<Sb, true, true, ST>), grid, dim3(kFwdAdamThreads),
-                                           fwd_lds_bytes(L), s, params, L, no_obs, no_idx, 0, 0, (int)B, ws.x, ws.h1,
-                                           ws.h2, ws.zpart, no_copy, stop, RowGather{}, ff, la, ws.h2mask, *af);
-                    } else {
-                        hipLaunchKernelGGL((k_fwd_hidden<Sb, true, false, ST>), grid, dim3(256), fwd_lds_bytes(L), s,
-                                           params, L, no_obs, no_idx, 0, 0, (int)B, ws.x, ws.h1, ws.h2, ws.zpart,
-                                           no_copy, stop, RowGather{}, ff, la, ws.h2mask, AdamFwd{});
-                    }
-                    GS_LAUNCH_CHECK("k_fwd_hidden<fused, bf16>");
-                    return GS_OK;
+                    return go_sb(Bf16Shape<Sh>{});
                 } else {
                     GS_REQUIRE(false, "precision bf16: no bf16 instantiation of the MLP chain for this shape");
                 }
             }
-            if (af) {   // forward carrying the previous minibatch's clip + Adam (dW1|db1 partials)
-                if constexpr (lagged_shape<Sh>()) {
-                    GS_REQUIRE((af->part1 ? af->aa.nrb > 0 : af->aa.nrb == 0) && af->aa.n_slots <= 512,
-                               "lagged Adam: bad slot / partial counts");
-                    hipLaunchKernelGGL((k_fwd_hidden<Sh, true, true, ST>), grid, dim3(kFwdAdamThreads),
-                                       fwd_lds_bytes(L), s, params, L, no_obs, no_idx, 0, 0, (int)B, ws.x, ws.h1,
-                                       ws.h2, ws.zpart, no_copy, stop, RowGather{}, ff, la, ws.h2mask, *af);
-                    GS_LAUNCH_CHECK("k_fwd_hidden<fused, adam>");
-                    return GS_OK;
-                } else {
-                    GS_REQUIRE(false, "lagged Adam: no compile-time instantiation for this shape");
-                }
-            }
-            hipLaunchKernelGGL((k_fwd_hidden<Sh, true, false, ST>), grid, dim3(256), fwd_lds_bytes(L), s, params, L,
-                               no_obs, no_idx, 0, 0, (int)B, ws.x, ws.h1, ws.h2, ws.zpart, no_copy, stop, RowGather{},
-                               ff, la, ws.h2mask, AdamFwd{});
-            GS_LAUNCH_CHECK("k_fwd_hidden<fused>");
-            return GS_OK;
-        };
-        return ff.act ? go(std::true_type{}) : go(std::false_type{});
+            return go_sb(sh);
+        }
     });
 }
 

@@ -65,10 +65,10 @@ EXPERIMENTS = {
                   "    const unsigned nblk = (unsigned)(sh0.nA + sh0.nB + sh0.nC);",
                   "    const unsigned nblk = (unsigned)((sh0.nA + sh0.nB + sh0.nC + 7) / 8 * 8);"),
                  ("gs_mlp.hip",
-                  "    GS_SPAN_T0\n    if (stop && *stop) return;\n    // multi-GPU: every output value goes through bwd_exchange",
-                  "    {\n        const BwdShape s0 = BwdShape::make(S::lay(Lrt), S::batch(Brt));\n"
+                  "    GS_SPAN_T0\n    GS_STAMP_T0\n    if constexpr (!FUSED)\n        if (stop && *stop) return;\n    // multi-GPU: every output value goes through bwd_exchange",
+                  "    {\n        const BwdShape s0 = BwdShape::make(S::lay(Lrt), S::batch(Brt), S::RB);\n"
                   "        if ((int)blockIdx.x >= s0.nA + s0.nB + s0.nC) return;\n    }\n"
-                  "    GS_SPAN_T0\n    if (stop && *stop) return;\n    // multi-GPU: every output value goes through bwd_exchange")],
+                  "    GS_SPAN_T0\n    GS_STAMP_T0\n    if constexpr (!FUSED)\n        if (stop && *stop) return;\n    // multi-GPU: every output value goes through bwd_exchange")],
     # role A tile (n-block, k-group) by n-block fastest: the 8 workgroups of an n-block share an XCD
     # with the forward workgroups that read their dW2 rows (with pad_bwd8)
     "roleA_xcd": [("gs_mlp.hip",

@@ -16,8 +16,10 @@ def main(dirs):
             for row in csv.DictReader(open(f)):
                 k = row.get("Kernel_Name", "")
                 short = k.split("(")[0].split("<")[0].replace("void ", "").replace("gs::", "")
-                if "fwd_hidden" in k and "true, true" in k:
+                if "k_fwd_chain" in k and ">, true" in k:      # k_fwd_chain<S, ADAM = true, ...>
                     short = "k_fwd_hidden<fused,adam>"
+                elif short == "k_bwd_chain":
+                    short = "k_bwd"
                 acc[short][row["Counter_Name"]].append(float(row["Counter_Value"]))
     out = {k: {c: sum(v[8:]) / max(1, len(v[8:])) for c, v in cs.items()} for k, cs in acc.items()}
     json.dump(out, sys.stdout, indent=1, sort_keys=True)

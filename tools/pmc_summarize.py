@@ -20,7 +20,14 @@ SHORT = ("k_fwd_hidden", "k_loss", "k_bwd", "k_clip_adam", "k_heads_act", "k_gae
 BY_GRID = ("k_gae_staged", "k_gae_f32")   # one kernel at several shapes: keyed by grid size
 
 
+# the fused chain's entries keep the keys of the kernels whose bodies they run (bench.py reads them)
+CHAIN = {"k_fwd_chain": "k_fwd_hidden", "k_bwd_chain": "k_bwd"}
+
+
 def short(name):
+    for c, s in CHAIN.items():
+        if re.search(r"\b" + c + r"\b", name):
+            return s
     for s in SHORT:
         if re.search(r"\b" + s + r"\b", name):
             return s

@@ -55,7 +55,7 @@ if not SPANS_ONLY:
     _lib.lib.gs_debug_stamps(acc.ctypes.data, cnt.ctypes.data)
 acc = (acc - acc0).reshape(8, 16).astype(np.float64)
 cnt = (cnt - cnt0).astype(np.float64)
-names = {0: ("k_fwd_hidden<fused, adam> (0,0)", ["loads landed (waitcnt: stamp build only)", "W1 fold + norm",
+names = {0: ("k_fwd_chain<adam> (0,0)", ["loads landed (waitcnt: stamp build only)", "W1 fold + norm",
                                                   "adam (W1, W2 rows, slices)", "operands in LDS", "h1", "mfma h2",
                                                   "h2 out + heads"]),
          1: ("k_loss", ["inputs + adv norm", "per-row loss/grad", "reduce", "metrics"]),
@@ -73,6 +73,8 @@ for k, (n, phases) in names.items():
     print(f"{n:18s} launches {int(cnt[k]):6d}  total {tot:8.0f} cyc = {tot / 2.4e3:6.2f} us")
     for i, ph in enumerate(phases):
         print(f"    {ph:24s} {per[i]:8.0f} cyc  {per[i] / 2.4e3:6.2f} us")
+    if per[15] > 0:      # GS_STAMP_ENTRY: kernel entry -> first vector load issued (inside the first phase)
+        print(f"    {'entry -> first vector load issued':24s} {per[15]:8.0f} cyc  {per[15] / 2.4e3:6.2f} us")
 
 # chain timeline of the second update's first 2048 minibatches (100 MHz device clock -> us):
 # kernel spans from the first workgroup start to the last wave end, and the gaps between kernels
