@@ -292,9 +292,25 @@ struct RolloutRows {                 // time-major (T, N) rows of the rollout bu
     uint8_t *done, *timeout;
 };
 
+// One-launch rollout of a device env with real dynamics (gs_mlp.hip k_rollout_env; the kinds
+// are include/gsamd.h's GS_ENV_CARTPOLE / GS_ENV_ACROBOT, obs dims 4 / 6, 2 / 3 actions)
+struct DynEnvArgs {
+    double *state;                   // [N][4]
+    int32_t *meta;                   // [N][3] {steps, episodes, pending}
+    float *ep_ret, *obs;             // [N], [N][D]
+    int32_t *ep_cnt;                 // [N] finished-episode counters (may be null)
+    float *ep_ret_sum, *ep_len_sum;
+    int max_steps;
+    uint64_t seed;
+    int64_t env_offset;
+};
+
 bool rollout_synth_fits(const Layout &L);
 int launch_rollout_synth(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
                          uint64_t counter0, const SynthEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
+bool rollout_env_fits(const Layout &L, int kind);
+int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                       uint64_t counter0, int kind, const DynEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
 
 inline int n_col_blocks(int H) { return (H + kTile - 1) / kTile; }
 inline int n_sumsq_slots(const Layout &L) { return n_col_blocks(L.H2) * n_col_blocks(L.H1) + 2 * n_col_blocks(L.H2) + 1; }

@@ -41,6 +41,8 @@
 #include "gs_common.h"
 #include "gs_xgmi_dev.h"
 #include "gs_synth_env.h"
+#include "gs_cartpole_env.h"
+#include "gs_acrobot_env.h"
 
 namespace gs {
 
@@ -1145,16 +1147,109 @@ __global__ __launch_bounds__(256) void k_heads_act(const float *__restrict__ P, 
 }
 
 // ------------------------------------------------------------------------------------
-// k_rollout_synth: a whole rollout of the synthetic env in one launch (C3-sized MLPs, whose
-// weights fit in LDS).  Workgroup = 16 envs (one MFMA row tile) for all T vector steps: the
+// k_rollout_env: a whole rollout of a device env in one launch (C3-sized MLPs, whose
+// weights fit in LDS), generic over the env E: the synthetic env, CartPole or Acrobot.  Workgroup = 16 envs (one MFMA row tile) for all T vector steps: the
 // policy's act with gs_policy_act's arithmetic in its order (h1 fmaf chain + bias; each h2
 // column block's 4 K-range MFMA partials summed in range order, as the 4 waves of
 // k_fwd_hidden do; partial heads per column block summed in block order as k_heads_act), so the
-// rows are bit-identical to the step-wise rollout; then the env step (gs_synth_env.h).  No
-// launch and no HBM round trip per step: the envs' observations stay in LDS.
+// rows are bit-identical to the step-wise rollout; then the env step (E::step, the arithmetic of
+// the env's own step kernel from its gs_*_env.h header).  No launch and no HBM round trip per
+// step: the envs' observations stay in LDS.
 // LDS (floats): W1 [H1*D] b1 [H1] W2 [H2][H1+4] b2 [H2] Wh [A1][H2] bh [round4(A1)] x [16][D]
 //               h1 [16][H1+4] h2 [ncb][16][17] zp [16][ncb][A1]
 // ------------------------------------------------------------------------------------
+// The env of a one-launch rollout: its state lives in the registers of threads 0..15 (one env
+// each) for the whole launch.  load / store move it from / to the env's device tensors, step
+// advances it by one vector step given the action and returns the step's reward / done / timeout,
+// next_obs (called by all 256 threads) leaves the next observations in the LDS rows xs [16][D].
+struct RolloutSynthEnv {
+    using Args = SynthEnvArgs;
+    int32_t st[3];
+    float er;
+    __device__ __forceinline__ void load(const Args &ev, int64_t me)
+    {
+        st[0] = ev.state[4 * me + 0];
+        st[1] = ev.state[4 * me + 1];
+        st[2] = ev.state[4 * me + 2];
+        er = ev.ep_ret[me];
+    }
+    __device__ __forceinline__ SynthStep step(const Args &ev, int64_t me, int64_t)
+    {
+        return synth_env_step(st, er, ev.L, ev.trunc_every, ev.reward, ev.ep_cnt ? ev.ep_cnt + me : nullptr,
+                              ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
+                              ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+    }
+    // observations after step0 + t + 1 vector steps: a hash per element, spread over the workgroup
+    __device__ __forceinline__ void next_obs(const Args &ev, float *xs, int64_t e0, int64_t N, int D, int t, int tid,
+                                             bool) const
+    {
+        for (int u = tid; u < kTile * D; u += 256) {
+            const int i = u / D;
+            if (e0 + i < N)
+                xs[u] = synth_obs(ev.seed, (uint64_t)(ev.env_offset + e0 + i), ev.step0 + (uint64_t)t + 1,
+                                  (uint64_t)(u - i * D));
+        }
+    }
+    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
+    {
+        ev.state[4 * me + 0] = st[0];
+        ev.state[4 * me + 1] = st[1];
+        ev.state[4 * me + 2] = st[2];
+        ev.ep_ret[me] = er;
+    }
+};
+
+// CartPole / Acrobot: State, its step and its observation come from the env's header
+template <class State, int OBS_DIM>
+struct RolloutDynEnvBase {
+    using Args = DynEnvArgs;
+    State s;
+    int32_t meta[3];
+    float er;
+    __device__ __forceinline__ void load(const Args &ev, int64_t me)
+    {
+        s = reinterpret_cast<const State *>(ev.state)[me];
+        meta[0] = ev.meta[3 * me + 0];
+        meta[1] = ev.meta[3 * me + 1];
+        meta[2] = ev.meta[3 * me + 2];
+        er = ev.ep_ret[me];
+    }
+    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
+    {
+        reinterpret_cast<State *>(ev.state)[me] = s;
+        ev.meta[3 * me + 0] = meta[0];
+        ev.meta[3 * me + 1] = meta[1];
+        ev.meta[3 * me + 2] = meta[2];
+        ev.ep_ret[me] = er;
+    }
+};
+struct RolloutCartPoleEnv : RolloutDynEnvBase<CPState, 4> {
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        return cartpole_env_step(s, meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me),
+                                 ev.ep_cnt ? ev.ep_cnt + me : nullptr, ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
+                                 ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+    }
+    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
+                                             bool env_thread) const
+    {
+        if (env_thread) cartpole_write_obs(s, xs + 4 * tid);
+    }
+};
+struct RolloutAcrobotEnv : RolloutDynEnvBase<ACState, 6> {
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        return acrobot_env_step(s, meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me),
+                                ev.ep_cnt ? ev.ep_cnt + me : nullptr, ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
+                                ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+    }
+    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
+                                             bool env_thread) const
+    {
+        if (env_thread) acrobot_write_obs(s, xs + 6 * tid);
+    }
+};
+
 size_t rollout_synth_lds_bytes(const Layout &L)
 {
     const int A1 = L.A + 1, ncb = (L.H2 + kTile - 1) / kTile;
@@ -1164,10 +1259,10 @@ size_t rollout_synth_lds_bytes(const Layout &L)
     return n * sizeof(float);
 }
 
-template <class S>
-__global__ __launch_bounds__(256) void k_rollout_synth(const float *__restrict__ P, Layout Lrt, int64_t N, int T,
-                                                       int mode, uint64_t rng_seed, uint64_t counter0, SynthEnvArgs ev,
-                                                       RolloutRows rw)
+template <class S, class E>
+__global__ __launch_bounds__(256) void k_rollout_env(const float *__restrict__ P, Layout Lrt, int64_t N, int T,
+                                                     int mode, uint64_t rng_seed, uint64_t counter0,
+                                                     typename E::Args ev, RolloutRows rw)
 {
     constexpr int AMAX = S::AMAX;
     const Layout L = S::lay(Lrt);
@@ -1203,14 +1298,8 @@ __global__ __launch_bounds__(256) void k_rollout_synth(const float *__restrict__
     // ---- this workgroup's envs: state in registers of threads 0..15, observations in LDS
     const int64_t me = e0 + (tid < kTile ? tid : 0);
     const bool env_thread = tid < kTile && me < N;
-    int32_t st[3] = {0, 0, 0};
-    float er = 0.0f;
-    if (env_thread) {
-        st[0] = ev.state[4 * me + 0];
-        st[1] = ev.state[4 * me + 1];
-        st[2] = ev.state[4 * me + 2];
-        er = ev.ep_ret[me];
-    }
+    E env{};
+    if (env_thread) env.load(ev, me);
     for (int u = tid; u < kTile * D; u += 256) {
         const int i = u / D;
         xs[u] = e0 + i < N ? ev.obs[(e0 + i) * D + (u - i * D)] : 0.0f;
@@ -1330,30 +1419,16 @@ __global__ __launch_bounds__(256) void k_rollout_synth(const float *__restrict__
             const int64_t o = row0 + me;
             head_act_row<AMAX>(z, A, mode, rng_seed, counter0 + (uint64_t)t, me, rw.actions + o, rw.logp + o,
                                rw.value + o);
-            const SynthStep so = synth_env_step(st, er, ev.L, ev.trunc_every, ev.reward,
-                                                ev.ep_cnt ? ev.ep_cnt + me : nullptr,
-                                                ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
-                                                ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+            const auto so = env.step(ev, me, rw.actions[o]);
             rw.reward[o] = so.reward;
             rw.done[o] = so.done ? 1 : 0;
             rw.timeout[o] = so.timeout ? 1 : 0;
         }
-        // next observations (after step0 + t + 1 vector steps)
-        for (int u = tid; u < kTile * D; u += 256) {
-            const int i = u / D;
-            if (e0 + i < N)
-                xs[u] = synth_obs(ev.seed, (uint64_t)(ev.env_offset + e0 + i), ev.step0 + (uint64_t)t + 1,
-                                  (uint64_t)(u - i * D));
-        }
+        env.next_obs(ev, xs, e0, N, D, t, tid, env_thread);
         __syncthreads();
     }
     // ---- the envs' state and observations back
-    if (env_thread) {
-        ev.state[4 * me + 0] = st[0];
-        ev.state[4 * me + 1] = st[1];
-        ev.state[4 * me + 2] = st[2];
-        ev.ep_ret[me] = er;
-    }
+    if (env_thread) env.store(ev, me);
     for (int u = tid; u < kTile * D; u += 256) {
         const int i = u / D;
         if (e0 + i < N) ev.obs[(e0 + i) * D + (u - i * D)] = xs[u];
@@ -1365,20 +1440,45 @@ bool rollout_synth_fits(const Layout &L)
     return L.H1 % kTile == 0 && L.H1 >= kTile && rollout_synth_lds_bytes(L) <= 160 * 1024;
 }
 
+template <class Sh, class E>
+int launch_rollout_sh(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                      uint64_t counter0, const typename E::Args &ev, const RolloutRows &rw, hipStream_t s)
+{
+    const size_t lds = rollout_synth_lds_bytes(L);
+    const dim3 grid((unsigned)((N + kTile - 1) / kTile));
+    int rc = set_lds_limit((const void *)k_rollout_env<Sh, E>, lds);
+    if (rc) return rc;
+    hipLaunchKernelGGL((k_rollout_env<Sh, E>), grid, dim3(256), lds, s, P, L, N, T, mode, rng_seed, counter0, ev, rw);
+    GS_LAUNCH_CHECK("k_rollout_env");
+    return GS_OK;
+}
+
 int launch_rollout_synth(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
                          uint64_t counter0, const SynthEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
 {
     GS_REQUIRE(rollout_synth_fits(L), "gs_rollout_synth: the policy does not fit in LDS");
-    const size_t lds = rollout_synth_lds_bytes(L);
-    const dim3 grid((unsigned)((N + kTile - 1) / kTile));
     return with_shape(L, 0, [&](auto sh) {
-        int rc = set_lds_limit((const void *)k_rollout_synth<decltype(sh)>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_rollout_synth<decltype(sh)>, grid, dim3(256), lds, s, P, L, N, T, mode, rng_seed,
-                           counter0, ev, rw);
-        GS_LAUNCH_CHECK("k_rollout_synth");
-        return GS_OK;
+        return launch_rollout_sh<decltype(sh), RolloutSynthEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
     });
+}
+
+// the env kinds of include/gsamd.h with real dynamics: the policy's shape must be the env's
+bool rollout_env_fits(const Layout &L, int kind)
+{
+    if (kind == GS_ENV_CARTPOLE) return L.D == 4 && L.A == 2 && rollout_synth_fits(L);
+    if (kind == GS_ENV_ACROBOT) return L.D == 6 && L.A == 3 && rollout_synth_fits(L);
+    return false;
+}
+
+// Neither env's dims are a compile-time shape of with_shape that fits in LDS (CartPole's
+// 4-256-256-2 does not fit), so both run on the runtime shape gs_policy_act takes for them.
+int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                       uint64_t counter0, int kind, const DynEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
+{
+    GS_REQUIRE(rollout_env_fits(L, kind), "gs_rollout_env: env kind %d does not take this policy in one launch", kind);
+    if (kind == GS_ENV_CARTPOLE)
+        return launch_rollout_sh<ShapeR<4>, RolloutCartPoleEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
+    return launch_rollout_sh<ShapeR<4>, RolloutAcrobotEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
 }
 
 // ------------------------------------------------------------------------------------

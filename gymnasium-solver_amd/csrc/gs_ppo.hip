@@ -147,6 +147,41 @@ extern "C" int gs_rollout_synth(const float *params, gs_mlp_dims dims, int64_t N
                                 (hipStream_t)stream);
 }
 
+extern "C" int gs_rollout_env_supported(gs_mlp_dims dims, int kind, int *supported)
+{
+    GS_REQUIRE(supported, "gs_rollout_env_supported: null output");
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    const Layout L = layout_of(dims);
+    *supported = (kind == GS_ENV_SYNTHETIC ? rollout_synth_fits(L) : rollout_env_fits(L, kind)) ? 1 : 0;
+    return GS_OK;
+}
+
+extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
+                              uint64_t rng_counter0, int kind, double *env_state, int32_t *env_meta,
+                              float *env_ep_ret, float *env_obs, int32_t max_steps, uint64_t env_seed,
+                              int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum, float *ep_len_sum,
+                              float *obs_rows, int64_t *action_rows, float *logp_rows, float *value_rows,
+                              float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows, void *stream)
+{
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_env: bad N / T");
+    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_env: mode %d not in {0,1,2}", mode);
+    GS_REQUIRE(kind == GS_ENV_CARTPOLE || kind == GS_ENV_ACROBOT,
+               "gs_rollout_env: env kind %d has no dynamics here (the synthetic env: gs_rollout_synth)", kind);
+    GS_REQUIRE(max_steps > 0, "gs_rollout_env: max_steps must be > 0");
+    GS_REQUIRE(params && env_state && env_meta && env_ep_ret && env_obs && obs_rows && action_rows && logp_rows &&
+                   value_rows && reward_rows && done_rows && timeout_rows,
+               "gs_rollout_env: null buffer");
+    if (T == 0) return GS_OK;
+    DynEnvArgs ev{env_state, env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
+                  env_seed, env_offset};
+    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return launch_rollout_env(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, kind, ev, rw,
+                              (hipStream_t)stream);
+}
+
 extern "C" int gs_policy_value(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, float *value,
                                void *scratch, void *stream)
 {

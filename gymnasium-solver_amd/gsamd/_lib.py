@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("GSAMD_LIB") or os.path.join(os.path.dirname(os.path.a
 GS_OK, GS_E_INVALID, GS_E_HIP, GS_E_COMM = 0, -1, -2, -3
 GS_ABI_VERSION = 7          # include/gsamd.h: the argument lists this binding declares
 GS_NUM_METRICS = 40
+GS_ENV_SYNTHETIC, GS_ENV_CARTPOLE, GS_ENV_ACROBOT = 0, 1, 2     # include/gsamd.h: gs_rollout_env kinds
 METRIC_SLOTS = (
     "loss", "policy_loss", "value_loss", "entropy", "clip_fraction", "clip_fraction_vf",
     "explained_var", "kl", "approx_kl", "adv_norm_mean", "adv_norm_std", "kl_stop", "grad_norm",
@@ -95,6 +96,9 @@ def _load():
         "gs_rollout_synth_supported": (ctypes.c_int, [MlpDims, vp]),
         "gs_rollout_synth": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, i32, i32, f32,
                                             u64, i64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_rollout_env_supported": (ctypes.c_int, [MlpDims, ctypes.c_int, vp]),
+        "gs_rollout_env": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, ctypes.c_int, vp, vp, vp, vp,
+                                          i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gs_env_reset": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, u64, i64, vp]),
         "gs_env_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, f32, u64, i64, u64, vp, vp, vp, vp, vp,
                                        vp, vp, vp]),
@@ -130,6 +134,8 @@ def _load():
                                       vp]),
         "gs_cartpole_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, u64, i64, vp]),
         "gs_cartpole_step": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_acrobot_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, u64, i64, vp]),
+        "gs_acrobot_step": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
         "gs_atari_preprocess": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),
         "gs_atari_render": (ctypes.c_int, [vp, i64, u64, i64, u64, vp]),
         "gs_atari_env_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, u64, i64, vp]),
@@ -165,14 +171,14 @@ lib = _load()
 EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_normalize_advantages_scratch_bytes", "gs_normalize_advantages",
             "gs_cnn_activation_stats", "gs_gae_f32", "gs_sampler_stream_i32", "gs_mlp_param_count",
             "gs_policy_scratch_bytes", "gs_policy_act", "gs_policy_value", "gs_rollout_synth_supported",
-            "gs_rollout_synth", "gs_env_reset", "gs_env_step",
+            "gs_rollout_synth", "gs_rollout_env_supported", "gs_rollout_env", "gs_env_reset", "gs_env_step",
             "gs_episode_stats", "gs_episode_window",
             "gs_ppo_workspace_bytes", "gs_ppo_minibatch_step", "gs_ppo_loss", "gs_mlp_activation_stats", "gs_ppo_stage", "gs_ppo_update",
             "gs_ppo_update_global", "gs_ppo_update_workspace_bytes",
             "gs_ppo_graph_cache_info", "gs_ppo_exchange_inside_bwd",
             "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
             "gs_cnn_ppo_update_global",
-            "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
+            "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
             "gs_comm_init", "gs_comm_xgmi_create", "gs_comm_xgmi_connect", "gs_comm_status", "gs_comm_error_record",
             "gs_comm_xgmi_set_colocation", "gs_comm_xgmi_set_bwd_exchange", "gs_comm_xgmi_reset",
             "gs_comm_allreduce_mean_f32", "gs_comm_allreduce_sum_f64", "gs_ppo_global_adv_stats",

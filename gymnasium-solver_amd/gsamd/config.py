@@ -68,11 +68,12 @@ class PPOConfig:
     episode_len: int = 200
     truncate_every: int = 0
     # which env the agent steps when the caller passes none (device_env_kind):
-    #   "auto"      the env_id's own dynamics where the device implements them (CartPole-v1),
+    #   "auto"      the env_id's own dynamics where the device implements them (CartPole-v1, Acrobot-v1),
     #               otherwise the caller must pass the host VectorEnv (raises if not)
     #   "synthetic" the fixed-length-episode synthetic env of SURVEY §8d (bench / tests), or the
     #               synthetic Atari frame source for rgb configs
     #   "cartpole"  device CartPole-v1 dynamics
+    #   "acrobot"   device Acrobot-v1 dynamics
     env_dynamics: str = "auto"
     # data-parallel semantics of a multi-rank update:
     #   "local"  every rank takes B-row minibatches of its own samples (weak scaling, global batch G·B)
@@ -181,15 +182,15 @@ class PPOConfig:
 _FIELDS = {f.name for f in dataclasses.fields(PPOConfig)}
 _ALIASES = {"LunarLander-v2": "LunarLander-v3"}
 
-ENV_DYNAMICS = ("auto", "synthetic", "cartpole")
+ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot")
 # env ids whose dynamics the device implements, as BaseAgent.build_env would build them from a
 # config without wrappers / env kwargs / observation normalisation
-DEVICE_DYNAMICS = {"CartPole-v1": "cartpole"}
+DEVICE_DYNAMICS = {"CartPole-v1": "cartpole", "Acrobot-v1": "acrobot"}
 
 
 def device_env_kind(cfg) -> Optional[str]:
     """The device env a config trains on when the caller passes no env: "synthetic",
-    "cartpole", or None when the config names an env the device does not simulate — the
+    "cartpole", "acrobot", or None when the config names an env the device does not simulate — the
     caller then passes the host VectorEnv the reference would build
     (agents/base_agent.py:129-192 → utils/environment.py:421-425 build_env_from_config)."""
     mode = str(getattr(cfg, "env_dynamics", None) or "auto")

@@ -29,7 +29,7 @@ from .atari_env import DeviceAtariVecEnv
 from .config import device_env_kind
 from .cnn import DeviceCNNActorCritic
 from .policy import DeviceMLPActorCritic
-from .rollout import DeviceCartPoleVecEnv, DeviceRolloutCollector, DeviceSyntheticVecEnv
+from .rollout import DeviceAcrobotVecEnv, DeviceCartPoleVecEnv, DeviceRolloutCollector, DeviceSyntheticVecEnv
 from .samplers import IndexStreamPrefetcher, MultiPassRandomSampler, index_stream, rank_share
 from .distributed import allreduce_sum_f64, broadcast_int, check_replicas, comm_status, world_active
 from . import distributed as _dist
@@ -59,7 +59,7 @@ class DevicePPOAgent:
         self.device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
         self.rank, self.world_size, self.comm = int(rank), int(world_size), comm
         self.use_graph = bool(use_graph)
-        self.one_launch = bool(one_launch)      # synthetic env + LDS-sized MLP: one-launch rollouts
+        self.one_launch = bool(one_launch)      # device env + LDS-sized MLP: one-launch rollouts
         self.track_stats = bool(track_stats)
         # schedulable hyper-parameters (base_agent.py:72-77)
         self.policy_lr = config.policy_lr
@@ -116,6 +116,11 @@ class DevicePPOAgent:
                 raise ValueError("env_dynamics='cartpole' needs vector observations of dim 4 and 2 actions")
             return DeviceCartPoleVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
                                         max_steps=int(c.max_episode_steps or 500), device=self.device)
+        if kind == "acrobot":
+            if self.is_pixel or c.resolved_obs_dim() != 6 or c.resolved_n_actions() != 3:
+                raise ValueError("env_dynamics='acrobot' needs vector observations of dim 6 and 3 actions")
+            return DeviceAcrobotVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
+                                       max_steps=int(c.max_episode_steps or 500), device=self.device)
         seed = c.seed if train else c.seed + 1000
         if self.is_pixel:
             return DeviceAtariVecEnv(n_envs=c.n_envs, n_actions=c.resolved_n_actions(), episode_len=c.episode_len,
@@ -769,8 +774,8 @@ class DevicePPOAgent:
 def build_agent(config, *args, **kwargs):
     """agents/__init__.py:1-8 for the device path.  Accepts a gsamd PPOConfig or the
     reference's own Config object (adapted by name, gsamd.config.from_reference_config).
-    The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1 steps on the
-    device CartPole dynamics; any other env_id needs env= / env_factory= (the host VectorEnv
+    The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1 and Acrobot-v1 step on
+    their device dynamics; any other env_id needs env= / env_factory= (the host VectorEnv
     the reference's build_env_from_config returns); the synthetic env only with
     env_dynamics='synthetic'."""
     from .config import from_reference_config

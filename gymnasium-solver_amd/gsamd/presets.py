@@ -1,9 +1,9 @@
 """Resolved configs of the BASELINE.json workloads and the model presets.
 
 PRESETS holds what the reference's load_config(...) resolves for each id (values taken
-from config/environments/{CartPole-v1,LunarLander-v3,ALE-Pong-v5,ALE-Breakout-v5}.yaml
-through utils/config.py; tests/golden/configs.json is the machine-generated record
-tests/test_config.py compares against).  MODEL_REGISTRY mirrors
+from config/environments/{CartPole-v1,LunarLander-v3,Acrobot-v1,ALE-Pong-v5,ALE-Breakout-v5}.yaml
+through utils/config.py; tests/golden/configs.json, and config_acrobot.json for Acrobot-v1:ppo, are
+the machine-generated records the tests compare against).  MODEL_REGISTRY mirrors
 utils/model_registry.py:17-76.
 """
 
@@ -36,6 +36,12 @@ PRESETS = {
         model_id="mlp_small", max_env_steps=5000000.0, obs_type="vector",
         spec={"action_space": {"discrete": 4}, "observation_space": {"default": "state",
                                                                      "variants": {"state": {"shape": [8]}}}}),
+    "Acrobot-v1:ppo": dict(
+        _COMMON, env_id="Acrobot-v1", project_id="Acrobot-v1", n_envs=32, n_steps=2048, batch_size=64,
+        n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, policy_lr=0.0003,
+        model_id="mlp_small", max_env_steps=1000000.0, obs_type="vector", accelerator="cpu",
+        spec={"action_space": {"discrete": 3}, "observation_space": {"default": "state",
+                                                                     "variants": {"state": {"shape": [6]}}}}),
     "ALE-Pong-v5:rgb_ppo": dict(
         _COMMON, env_id="ALE/Pong-v5", project_id="ALE-Pong-v5_rgb", n_envs=32, n_steps=256, batch_size=1024,
         n_epochs=15, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.01, policy_lr=0.0003,

@@ -30,7 +30,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import check, lib, ptr, stream_handle
+from ._lib import GS_ENV_ACROBOT, GS_ENV_CARTPOLE, check, lib, ptr, stream_handle
 from .distributed import allreduce_sum_f64
 from .rollout_stats import RollingWindow
 
@@ -80,6 +80,7 @@ class DeviceCartPoleVecEnv:
     episodes is unpinned (reset draws use a counter hash, not PCG64)."""
 
     device_native = True
+    env_kind = GS_ENV_CARTPOLE       # gs_rollout_env's kind: one-launch rollouts when the policy fits in LDS
 
     def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, device="cuda", **_):
         self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 4, 2
@@ -107,6 +108,45 @@ class DeviceCartPoleVecEnv:
                                    self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
                                    ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
                                    ptr(self.ep_len_sum), stream_handle()), "gs_cartpole_step")
+
+
+class DeviceAcrobotVecEnv:
+    """Acrobot-v1 on device (gymnasium 1.x "book" dynamics restated in
+    csrc/gs_acrobot_env.h: RK4 of dt 0.2 in double precision, NEXT_STEP autoreset, TimeLimit 500).
+    Parity with gymnasium's own episodes is unpinned (reset draws use a counter hash, not PCG64)."""
+
+    device_native = True
+    env_kind = GS_ENV_ACROBOT
+    # One-launch rollouts are the default only up to this many envs: past it the graph-replayed
+    # step loop measured faster (DESIGN.md §4.1, profiles/acrobot_collect.json).  None = always.
+    one_launch_max_envs = None
+
+    def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, device="cuda", **_):
+        self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 6, 3
+        self.seed, self.env_offset, self.max_steps = int(seed), int(env_offset), int(max_steps)
+        self.obs_shape, self.obs_dtype = (6,), torch.float32
+        self.device = torch.device(device)
+        N, z = self.num_envs, dict(device=self.device)
+        self.state = torch.zeros(N, 4, dtype=torch.float64, **z)      # theta1, theta2, omega1, omega2
+        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
+        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
+        self.obs = torch.zeros(N, 6, dtype=torch.float32, **z)
+        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
+        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
+        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
+
+    def reset(self):
+        check(lib.gs_acrobot_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.num_envs,
+                                   self.seed, self.env_offset, stream_handle()), "gs_acrobot_reset")
+        return self.obs, {}
+
+    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
+        if actions is None:
+            raise ValueError("Acrobot dynamics need the step's actions")
+        check(lib.gs_acrobot_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), ptr(actions),
+                                  self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
+                                  ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
+                                  ptr(self.ep_len_sum), stream_handle()), "gs_acrobot_step")
 
 
 class DeviceRolloutBuffer:
@@ -235,10 +275,11 @@ class DeviceRolloutCollector:
         # per sampling mode into a hipGraph and replayed; the per-rollout counters reach the
         # kernels through a 2-word device clock (include/gsamd.h "Rollout clock")
         self.use_graph = bool(use_graph)
-        # the synthetic device env with a policy that fits in LDS: the whole rollout is one
-        # launch (gs_rollout_synth, rows bit-identical to the step-wise loop)
-        self.one_launch = bool(one_launch) and isinstance(env, DeviceSyntheticVecEnv) and \
-            hasattr(policy_model, "dims") and self._synth_supported(policy_model)
+        # a device env with a policy that fits in LDS: the whole rollout is one launch
+        # (gs_rollout_synth for the synthetic env, gs_rollout_env for an env that declares its
+        # env_kind; rows bit-identical to the step-wise loop)
+        self.one_launch = bool(one_launch) and hasattr(policy_model, "dims") and \
+            self._one_launch_supported(env, policy_model)
         self._graphs = {}
         self._clock = None
         self.total_rollouts = self.total_steps = self.total_vec_steps = self.total_episodes = 0
@@ -360,15 +401,33 @@ class DeviceRolloutCollector:
         return DeviceTrajectory(buf)
 
     @staticmethod
-    def _synth_supported(pm) -> bool:
+    def _one_launch_supported(env, pm) -> bool:
         v = ctypes.c_int()
-        check(lib.gs_rollout_synth_supported(pm.dims, ctypes.byref(v)), "gs_rollout_synth_supported")
+        if isinstance(env, DeviceSyntheticVecEnv):
+            check(lib.gs_rollout_synth_supported(pm.dims, ctypes.byref(v)), "gs_rollout_synth_supported")
+            return bool(v.value)
+        kind = getattr(env, "env_kind", None)
+        if kind is None or not getattr(env, "device_native", False):
+            return False
+        cap = getattr(env, "one_launch_max_envs", None)
+        if cap is not None and int(env.num_envs) > int(cap):
+            return False
+        check(lib.gs_rollout_env_supported(pm.dims, int(kind), ctypes.byref(v)), "gs_rollout_env_supported")
         return bool(v.value)
 
     def _collect_one_launch(self, mode):
-        """The T vector steps as one gs_rollout_synth launch (policy act + env step per step,
-        envs resident in LDS); the env's host step counter advances by T."""
+        """The T vector steps as one launch (policy act + env step per step, envs resident in
+        LDS): gs_rollout_env for an env with real dynamics, else gs_rollout_synth, after which
+        the synthetic env's host step counter advances by T."""
         buf, pm, env = self._buffer, self.policy_model, self.env
+        if not isinstance(env, DeviceSyntheticVecEnv):
+            check(lib.gs_rollout_env(ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed,
+                                     self.total_vec_steps, int(env.env_kind), ptr(env.state), ptr(env.meta),
+                                     ptr(env.ep_ret), ptr(env.obs), env.max_steps, env.seed, env.env_offset,
+                                     ptr(env.ep_count), ptr(env.ep_ret_sum), ptr(env.ep_len_sum), ptr(buf.obs),
+                                     ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values), ptr(buf.rewards),
+                                     ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_env")
+            return
         check(lib.gs_rollout_synth(ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed,
                                    self.total_vec_steps, ptr(env.state), ptr(env.ep_ret), ptr(env.obs),
                                    env.episode_len, env.truncate_every, env.reward, env.seed, env.env_offset,

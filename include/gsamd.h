@@ -138,6 +138,26 @@ int gs_rollout_synth(const float *params_dev, gs_mlp_dims dims, int64_t N, int64
                      float *obs_rows_dev, int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev,
                      float *reward_rows_dev, uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
 
+/* The same one-launch rollout on a device env with real dynamics: kind GS_ENV_CARTPOLE
+ * (gs_cartpole_*: obs dim 4, 2 actions) or GS_ENV_ACROBOT (gs_acrobot_*: obs dim 6, 3 actions).
+ * gs_rollout_env_supported: *supported_host = 1 when dims are that env's and the policy fits in
+ * LDS (kind GS_ENV_SYNTHETIC answers as gs_rollout_synth_supported).  gs_rollout_env: env_state_dev
+ * / env_meta_dev / env_ep_ret_dev / env_obs_dev and the episode counters are the env's tensors as
+ * its gs_*_step takes them; every row, the final env state / meta / observations and the episode
+ * counters equal T calls of gs_policy_act + the env's gs_*_step bit for bit, in all three modes
+ * and with a ragged last workgroup (N % 16 != 0).  The env's arithmetic is the step kernel's own
+ * (csrc/gs_cartpole_env.h, csrc/gs_acrobot_env.h). */
+#define GS_ENV_SYNTHETIC 0
+#define GS_ENV_CARTPOLE 1
+#define GS_ENV_ACROBOT 2
+int gs_rollout_env_supported(gs_mlp_dims dims, int kind, int *supported_host);
+int gs_rollout_env(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
+                   uint64_t rng_counter0, int kind, double *env_state_dev, int32_t *env_meta_dev,
+                   float *env_ep_ret_dev, float *env_obs_dev, int32_t max_steps, uint64_t env_seed, int64_t env_offset,
+                   int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, float *obs_rows_dev,
+                   int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev, float *reward_rows_dev,
+                   uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
+
 /* Value-only forward (utils/policy_ops.py:37-42 policy_predict_values), e.g. the
  * bootstrap value of the last observation (utils/rollout_collector.py:373). */
 int gs_policy_value(const float *params_dev, gs_mlp_dims dims, const float *obs_dev, int64_t N,
@@ -453,6 +473,23 @@ int gs_cartpole_step(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, fl
                      const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed, int64_t env_offset,
                      float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
                      int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
+
+/* ---------------------------------------------------------------- Acrobot-v1 dynamics (f1)
+ * gymnasium 1.x AcrobotEnv.step ("book" variant, no torque noise) restated on device: state
+ * {theta1, theta2, omega1, omega2} in double precision, one classical RK4 step of dt 0.2 under
+ * torque action - 1, angles wrapped into [-pi, pi] (at most 16 turns each way, so a non-finite
+ * state cannot spin), velocities clamped to 4 pi / 9 pi, terminated when
+ * -cos(theta1) - cos(theta1 + theta2) > 1, reward -1 (0 on the terminating step), TimeLimit
+ * max_steps, NEXT_STEP autoreset.  obs_dev: (N, 6) f32 {cos t1, sin t1, cos t2, sin t2, w1, w2}.
+ * state_dev / meta_dev / actions_dev / rows / counters as gs_cartpole_step.  Reset draws are
+ * uniform in [-0.1, 0.1) from the counter hash, rounded to float32 (gymnasium's PCG64 stream is
+ * not reproduced: parity with gymnasium's own episodes is unpinned, as for CartPole). */
+int gs_acrobot_reset(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, int64_t N,
+                     uint64_t seed, int64_t env_offset, void *stream);
+int gs_acrobot_step(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev,
+                    const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed, int64_t env_offset,
+                    float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
+                    int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
 
 /* The fp32 MFMA GEMM under the CNN path (convolutions as GEMMs, fc, heads), exported for its
  * tests: row-major C[M][N] = op(A) op(B) + beta C (+ bias[n]) (ReLU if relu), op(X) = X^T
