@@ -36,6 +36,7 @@
 #include <float.h>
 
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "gs_common.h"
@@ -290,6 +291,68 @@ __device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int 
 constexpr int kFwdAdamThreads = GS_FWD_ADAM_NT;
 static_assert(kFwdAdamThreads == 256 || kFwdAdamThreads == 512, "lagged forward: 256 or 512 threads");
 
+// Wave classes of the lagged forward's prologue.  A vector load returns a full wave's registers
+// whatever its lanes do with them, so a wave issues only the dW1|db1 partial quads and W1|b1 quads
+// that at least one of its lanes consumes.  What wave w needs is known at compile time:
+//   nrm(w): it takes part in the global norm (threads 0..255) and reads the per-tile slots
+//   npq(w): norm partial quads j < NQ with 256*j + 64*w < NQ1 (0 past the norm waves)
+//   nw1(w): W1|b1 quads j < NQP with NT*j + 64*w < NQ1
+// All three fall with w, so the waves of one class are a contiguous range [w, end(w)).
+// Each class is its own copy of the prologue (its own instruction stream to fetch; the kernel
+// more than doubles), which has to be paid for by the loads it removes: C2 (NRB = 8 row-block
+// partials per quad, 97 dead float4 wave-loads of 216 per workgroup) gains by it, C3 (NRB = 2,
+// 31 of 88, a 32-workgroup grid) measured slower with the split.  So
+// the split is on only from kMinDeadWaveLoads dead float4 wave-loads per workgroup; below it
+// there is one class whose waves all issue every load (the lanes that take no part discard theirs).
+constexpr int kMinDeadWaveLoads = 64;
+template <int NT, int NQ1, int NRB>
+struct FwdWaveClasses {
+    static constexpr int NW = NT / 64, NQ = (NQ1 + 255) / 256, NQP = (NQ1 + NT - 1) / NT;
+    static constexpr int live_npq(int w)
+    {
+        int n = 0;
+        for (int j = 0; j < NQ; ++j) n += w < 4 && 256 * j + 64 * w < NQ1;
+        return n;
+    }
+    static constexpr int live_nw1(int w)
+    {
+        int n = 0;
+        for (int j = 0; j < NQP; ++j) n += NT * j + 64 * w < NQ1;
+        return n;
+    }
+    static constexpr int dead_wave_loads()
+    {
+        int n = 0;
+        for (int w = 0; w < NW; ++w) n += (NQ - live_npq(w)) * NRB + (NQP - live_nw1(w)) * 3;
+        return n;
+    }
+    static constexpr bool kSplit = dead_wave_loads() >= kMinDeadWaveLoads;
+    static constexpr bool nrm(int w) { return !kSplit || w < 4; }
+    static constexpr int npq(int w) { return kSplit ? live_npq(w) : NQ; }
+    static constexpr int nw1(int w) { return kSplit ? live_nw1(w) : NQP; }
+    static constexpr bool same(int a, int b) { return nrm(a) == nrm(b) && npq(a) == npq(b) && nw1(a) == nw1(b); }
+    static constexpr int end(int w)
+    {
+        int e = w + 1;
+        while (e < NW && same(w, e)) ++e;
+        return e;
+    }
+};
+// f(integral_constant<first wave of wv's class>): one scalar compare per class boundary
+template <class WC, int W, class F>
+__device__ __forceinline__ void for_wave_class(int wv, F &&f)
+{
+    constexpr int E = WC::end(W);
+    if constexpr (E >= WC::NW) {
+        f(std::integral_constant<int, W>{});
+    } else {
+        if (wv < E)
+            f(std::integral_constant<int, W>{});
+        else
+            for_wave_class<WC, E>(wv, f);
+    }
+}
+
 // STATS (GS_HP_ACT_STATS, fused chain): the workgroup also records the activation statistics of its
 // rows (FusedFwd::act, kActRec words): dead counts of the 16 h1 columns of chunk cb and of its 16 h2
 // columns and the float sums of z and z^2 of both (the pre-activation values of the forward hooks on
@@ -362,11 +425,6 @@ __device__ __forceinline__ void fwd_hidden_body(
         // multi-GPU chain: the exchange has already folded dW1|db1 into G (parameter order) and
         // its per-workgroup sums of squares cover the whole gradient (k_clip_adam<S, 0, 0>'s order)
         const bool fold = af.part1 != nullptr;
-        const int64_t kprev = kstep - 1 + af.force;
-        const bool apply = kprev >= 0;
-        const bool own1 = apply && cb == 0 && rb == 0, own2 = apply && rb == 0;
-        const bool stW2[3] = {own2, own2, own2};
-        const bool stW1[3] = {own1, own1, own1};
         const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
         // global-address-space float4 loads (the AdamFwd pointers would otherwise lower to flat,
         // and a predicated float4 select to four dword loads); the moment / gradient buffers are
@@ -376,176 +434,216 @@ __device__ __forceinline__ void fwd_hidden_body(
             return make_float4(v[0], v[1], v[2], v[3]);
         };
         auto ld1 = [](const float *base, int64_t o) { return *(const __attribute__((address_space(1))) float *)(base + o); };
-        // Every vector load below is unconditional, at an index clamped into its array, and the
-        // lanes past an array's end discard what they loaded: a predicated load (`ok ? load : 0`)
-        // compiles to an exec-masked branch per load, and the register moves around those
-        // branches force s_waitcnt vmcnt stalls in the middle of the burst (one memory round trip
-        // per stall instead of one for the whole prologue)
+        // Every vector load a wave issues below is unconditional, at an index clamped into its
+        // array, and the lanes past an array's end discard what they loaded: a predicated load
+        // (`ok ? load : 0`) compiles to an exec-masked branch per load, and the register moves
+        // around those branches force s_waitcnt vmcnt stalls in the middle of the burst (one
+        // memory round trip per stall instead of one for the whole prologue).  A wave-uniform
+        // guard around single loads does the same (scalar branches, a loaded register meeting a
+        // constant at the join).  So the choice of which loads a wave issues at all is made once,
+        // at the top: the whole prologue, first load to Adam stores, is straight-line code per
+        // wave class (FwdWaveClasses), selected by a scalar branch, and nothing loaded in one
+        // class meets another class's value before it is consumed.  Every class runs the same
+        // barriers.
         constexpr int nq1 = n1 / 4;
+        using WC = FwdWaveClasses<NT, nq1, NRB>;
+        static_assert(WC::NQ == NQ, "norm partial quads");
         // Adam: W1|b1 quad q = tid + NT*j; norm partials: threads 0..255, quad tid + 256*j (the
-        // 256-thread grouping of k_clip_adam, wave-uniform branch for the wider block)
-        constexpr int NQP = (nq1 + NT - 1) / NT;
-        const bool nrm = NT == 256 || tid < 256;
-        // The lanes that take no part in the norm (waves 4..7 of a 512-thread block) load quad 0,
-        // and without the fold (G already holds dW1|db1) every partial slot re-reads G: no load
-        // sits in a branch, and no loaded register is merged with a constant at a join — either
-        // puts an s_waitcnt vmcnt(0) inside the burst, a memory round trip each.  The unused
-        // values are dropped where they are consumed.
-        // Issue order = the order the phases consume them (vmcnt counts in order): the norm's
-        // slots and partials first, so the fold + norm start while the Adam operands are in flight.
-        float sl[NS];     // slots past n_slots and the non-norm lanes are dropped in the norm
-#pragma unroll
-        for (int j = 0; j < NS; ++j) sl[j] = ld1(af.sumsq, nrm ? min(tid + 256 * j, aa.n_slots - 1) : 0);
-        GS_STAMP_ENTRY
-        float4 w1p[NQP], w1m[NQP], w1v[NQP], t[NQ][NRB];  // W1|b1 (param order), dW1|db1 partials
+        // 256-thread grouping of k_clip_adam)
         const float *tsrc = fold ? af.part1 : af.G;
         const int64_t tstride = fold ? (int64_t)n1 : 0;
         const int nrb_used = fold ? NRB : 1;
+        auto prologue = [&](auto first_wave) __attribute__((always_inline)) {
+            constexpr int W0 = decltype(first_wave)::value;
+            constexpr bool nrmc = WC::nrm(W0);                      // this wave loads the norm's operands
+            // ... and takes part in the norm (without the split every wave loads, threads 0..255 take
+            // part, and the other waves' lanes all load element 0: one line per wave-load; distinct
+            // clamped addresses there measured 0.2 us per minibatch slower on C3)
+            const bool nrm = nrmc && (WC::kSplit || NT == 256 || tid < 256);
+            constexpr int NPQ = WC::npq(W0), NQP = WC::nw1(W0);     // its live partial / W1|b1 quads
+            // Without the fold (G already holds dW1|db1) every partial slot re-reads G (no branch
+            // around the other row blocks' loads); the unused values are dropped in the fold.
+            // Issue order = the order the phases consume them (vmcnt counts in order): the norm's
+            // slots and partials first, so the fold + norm start while the Adam operands are in flight.
+            float sl[nrmc ? NS : 1];     // slots past n_slots are dropped in the norm
+            if constexpr (nrmc)
 #pragma unroll
-        for (int j = 0; j < NQ; ++j)
+                for (int j = 0; j < NS; ++j) sl[j] = ld1(af.sumsq, nrm ? min(tid + 256 * j, aa.n_slots - 1) : 0);
+            GS_STAMP_ENTRY
+            // W1|b1 (param order), dW1|db1 partials
+            float4 w1p[NQP > 0 ? NQP : 1], w1m[NQP > 0 ? NQP : 1], w1v[NQP > 0 ? NQP : 1], t[NPQ > 0 ? NPQ : 1][NRB];
 #pragma unroll
-            for (int b = 0; b < NRB; ++b)
-                t[j][b] = ld4(tsrc + (int64_t)b * tstride, nrm ? min(tid + 256 * j, nq1 - 1) : 0);
+            for (int j = 0; j < NPQ; ++j)
 #pragma unroll
-        for (int j = 0; j < NQP; ++j) {
-            const int q = min(tid + NT * j, nq1 - 1);
-            w1p[j] = ld4(P, q);
-            w1m[j] = ld4(af.Min, q);
-            w1v[j] = ld4(af.Vin, q);
-        }
-        float4 w2m[kW2v], w2v[kW2v], w2g[kW2v];           // this workgroup's 16 W2 rows
+                for (int b = 0; b < NRB; ++b)
+                    t[j][b] = ld4(tsrc + (int64_t)b * tstride, nrm ? min(tid + 256 * j, nq1 - 1) : 0);
 #pragma unroll
-        for (int j = 0; j < kW2v; ++j) {
-            const int u = tid + NT * j, i = u / k4n, k4 = u - i * k4n;
-            const int64_t q = (Lc.oW2 + (int64_t)min(c0 + i, H2 - 1) * cH1) / 4 + k4;
-            w2r[j] = ld4(P, q);
-            w2m[j] = ld4(af.Min, q);
-            w2v[j] = ld4(af.Vin, q);
-            w2g[j] = ld4(af.G, q);
-        }
-        // scalar slices {p, m, v, g}: b2 (threads < 16), head weights (< 16*A1), head biases ((0,0), < A1)
-        const int64_t ob = tid < kTile && c0 + tid < H2 ? Lc.ob2 + c0 + tid : -1;
-        const int64_t ow = tid < cA1 * kTile && c0 + (tid & 15) < H2 ? Lc.head_row(tid >> 4) + c0 + (tid & 15) : -1;
-        const int64_t oh = own1 && tid < cA1 ? Lc.head_bias(tid) : -1;
-        float sb[4], sw[4], shb[4];
-        auto load_slice = [&](float (&e)[4], int64_t o) {
-            const int64_t oc = o < 0 ? 0 : o;
-            e[0] = ld1(P, oc);
-            e[1] = ld1(af.Min, oc);
-            e[2] = ld1(af.Vin, oc);
-            e[3] = ld1(af.G, oc);
-        };
-        load_slice(sb, ob);
-        load_slice(sw, ow);
-        load_slice(shb, oh);
-        // then the loads behind the graph replay's step base: this minibatch's x rows (stored to
-        // LDS after the Adam step, where nothing waits for them) and step k-1's schedule entries
-        const bool okx = tid < kTile * cD && r0 + min(tid / cD, kTile - 1) < rows;
-        const float xv = ff.xg[(kstep * rows + r0) * cD + (okx ? tid : 0)];
-        const float neg_step = apply && aa.sched ? aa.sched[2 * kprev] : aa.neg_step_size;
-        const float bc2s = apply && aa.sched ? aa.sched[2 * kprev + 1] : aa.inv_bc2_sqrt;
-#ifdef GS_STAMPS
-        __builtin_amdgcn_s_waitcnt(0);     // diagnostic build only: split "loads landed" from the norm
-        __syncthreads();
-#endif
-        GS_STAMP(0)
-        // global norm -> clip coefficient: the per-tile slots, then the folded dW1|db1 (k_clip_adam's order)
-        float coef = 0.0f;
-        float *w1g = h1s;      // dW1|db1: part1 order when folded here, else parameter order (h1s is unused until phase 1)
-        if (apply) {
-            double ss = 0.0;
-#pragma unroll
-            for (int j = 0; j < NS; ++j)
-                if (nrm && tid + 256 * j < aa.n_slots) ss += (double)sl[j];
-#pragma unroll
-            for (int j = 0; j < NQ; ++j) {
-                if (!nrm) break;
-                float4 g = z4;
-#pragma unroll
-                for (int b = 0; b < NRB; ++b) {
-                    if (b >= nrb_used) break;
-                    g.x += t[j][b].x;
-                    g.y += t[j][b].y;
-                    g.z += t[j][b].z;
-                    g.w += t[j][b].w;
-                }
-                if (4 * (tid + 256 * j) < n1) {
-                    reinterpret_cast<float4 *>(w1g)[tid + 256 * j] = g;
-                    if (fold) {
-                        ss += (double)g.x * (double)g.x;
-                        ss += (double)g.y * (double)g.y;
-                        ss += (double)g.z * (double)g.z;
-                        ss += (double)g.w * (double)g.w;
-                    }
-                }
+            for (int j = 0; j < NQP; ++j) {
+                const int q = min(tid + NT * j, nq1 - 1);
+                w1p[j] = ld4(P, q);
+                w1m[j] = ld4(af.Min, q);
+                w1v[j] = ld4(af.Vin, q);
             }
-            double tt[1] = {ss};
-            block_reduce<1>(tt, reinterpret_cast<double *>(red));   // its barriers also publish w1g
-            const float total = (float)sqrt(tt[0]) * aa.grad_scale;
-            coef = clip_coef(total, aa) * aa.grad_scale;
-            if (own1 && tid == 0 && af.metrics) af.metrics[kprev * GS_NUM_METRICS + GS_M_GRAD_NORM] = total;
-            if (own1 && tid == 0 && aa.normsq)
-                aa.normsq[kprev] = tt[0] * (double)aa.grad_scale * (double)aa.grad_scale;
-        }
-        GS_STAMP(1)
-        // Adam on the owned parameters: new values to LDS / registers, and from row block 0 to the other set
-#pragma unroll
-        for (int j = 0; j < NQP; ++j) {
-            const int q = tid + NT * j;
-            if (4 * q >= n1) continue;
-            float4 p4 = w1p[j];
-            if (apply) {
-                float p[4] = {p4.x, p4.y, p4.z, p4.w};
-                float m[4] = {w1m[j].x, w1m[j].y, w1m[j].z, w1m[j].w};
-                float v[4] = {w1v[j].x, w1v[j].y, w1v[j].z, w1v[j].w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    adam_param(w1g[fold ? part1_index(Lc, 4 * q + e) : 4 * q + e], coef, m[e], v[e], p[e], aa,
-                               neg_step, bc2s);
-                p4 = make_float4(p[0], p[1], p[2], p[3]);
-                // the new W1|b1 p / m / v are stored by three different workgroups of row block 3
-                // (workgroup-uniform choice: one workgroup storing all three drained last)
-                if (stW1[0]) reinterpret_cast<float4 *>(af.Pout)[q] = p4;
-                if (stW1[1]) reinterpret_cast<float4 *>(af.Mout)[q] = make_float4(m[0], m[1], m[2], m[3]);
-                if (stW1[2]) reinterpret_cast<float4 *>(af.Vout)[q] = make_float4(v[0], v[1], v[2], v[3]);
-            }
-            reinterpret_cast<float4 *>(W1s)[q] = p4;
-        }
-        if (apply) {
+            float4 w2m[kW2v], w2v[kW2v], w2g[kW2v];           // this workgroup's 16 W2 rows
 #pragma unroll
             for (int j = 0; j < kW2v; ++j) {
                 const int u = tid + NT * j, i = u / k4n, k4 = u - i * k4n;
-                if (c0 + i >= H2) continue;
-                float p[4] = {w2r[j].x, w2r[j].y, w2r[j].z, w2r[j].w};
-                float m[4] = {w2m[j].x, w2m[j].y, w2m[j].z, w2m[j].w};
-                float v[4] = {w2v[j].x, w2v[j].y, w2v[j].z, w2v[j].w};
-                const float g[4] = {w2g[j].x, w2g[j].y, w2g[j].z, w2g[j].w};
+                const int64_t q = (Lc.oW2 + (int64_t)min(c0 + i, H2 - 1) * cH1) / 4 + k4;
+                w2r[j] = ld4(P, q);
+                w2m[j] = ld4(af.Min, q);
+                w2v[j] = ld4(af.Vin, q);
+                w2g[j] = ld4(af.G, q);
+            }
+            // Everything above needs only the preloaded arguments.  `apply` and the owner flags come
+            // from the argument tail (af.force), whose scalar loads land under the burst: they are
+            // formed here, per class (the class number in the statement keeps the compiler from
+            // hoisting them, and the wait for the tail, above the class branch and the first load;
+            // the scheduling barrier keeps that wait behind the last load above; the statement's
+            // result counts as divergent, hence the readfirstlane: `apply` stays a scalar)
+            int force = af.force;
+            if constexpr (WC::kSplit) {
+                __builtin_amdgcn_sched_barrier(0);
+                asm volatile("; lagged forward: wave class %1" : "+s"(force) : "n"(W0));
+                force = __builtin_amdgcn_readfirstlane(force);
+            }
+            const int64_t kprev = kstep - 1 + force;
+            const bool apply = kprev >= 0;
+            const bool own1 = apply && cb == 0 && rb == 0, own2 = apply && rb == 0;
+            const bool stW2[3] = {own2, own2, own2};
+            const bool stW1[3] = {own1, own1, own1};
+            // step k-1's schedule entries, ahead of the slices: with the class split they are vector
+            // loads (vmcnt counts in order), and the Adam step, which needs them first, must not
+            // wait for the slices and x behind them (without the split they are scalar loads and
+            // keep their place behind x)
+            float neg_step = aa.neg_step_size, bc2s = aa.inv_bc2_sqrt;
+            auto load_sched = [&]() {
+                if (apply && aa.sched) neg_step = aa.sched[2 * kprev], bc2s = aa.sched[2 * kprev + 1];
+            };
+            if constexpr (WC::kSplit) load_sched();
+            // scalar slices {p, m, v, g}: b2 (threads < 16), head weights (< 16*A1), head biases ((0,0), < A1)
+            const int64_t ob = tid < kTile && c0 + tid < H2 ? Lc.ob2 + c0 + tid : -1;
+            const int64_t ow = tid < cA1 * kTile && c0 + (tid & 15) < H2 ? Lc.head_row(tid >> 4) + c0 + (tid & 15) : -1;
+            const int64_t oh = own1 && tid < cA1 ? Lc.head_bias(tid) : -1;
+            float sb[4], sw[4], shb[4];
+            auto load_slice = [&](float (&e)[4], int64_t o) {
+                const int64_t oc = o < 0 ? 0 : o;
+                e[0] = ld1(P, oc);
+                e[1] = ld1(af.Min, oc);
+                e[2] = ld1(af.Vin, oc);
+                e[3] = ld1(af.G, oc);
+            };
+            load_slice(sb, ob);
+            load_slice(sw, ow);
+            load_slice(shb, oh);
+            // then the loads behind the graph replay's step base: this minibatch's x rows (stored to
+            // LDS after the Adam step, where nothing waits for them)
+            const bool okx = tid < kTile * cD && r0 + min(tid / cD, kTile - 1) < rows;
+            const float xv = ff.xg[(kstep * rows + r0) * cD + (okx ? tid : 0)];
+            if constexpr (!WC::kSplit) load_sched();
+#ifdef GS_STAMPS
+            __builtin_amdgcn_s_waitcnt(0);     // diagnostic build only: split "loads landed" from the norm
+            __syncthreads();
+#endif
+            GS_STAMP(0)
+            // global norm -> clip coefficient: the per-tile slots, then the folded dW1|db1 (k_clip_adam's order)
+            float coef = 0.0f;
+            float *w1g = h1s;      // dW1|db1: part1 order when folded here, else parameter order (h1s is unused until phase 1)
+            if (apply) {
+                double ss = 0.0;
+                if constexpr (nrmc)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) adam_param(g[e], coef, m[e], v[e], p[e], aa, neg_step, bc2s);
-                w2r[j] = make_float4(p[0], p[1], p[2], p[3]);
-                // this column block's 16 new W2 rows: p by row block 0, m by 1, v by 2 (16 KB each)
-                const int64_t q = (Lc.oW2 + (int64_t)(c0 + i) * cH1) / 4 + k4;
-                if (stW2[0]) reinterpret_cast<float4 *>(af.Pout)[q] = w2r[j];
-                if (stW2[1]) reinterpret_cast<float4 *>(af.Mout)[q] = make_float4(m[0], m[1], m[2], m[3]);
-                if (stW2[2]) reinterpret_cast<float4 *>(af.Vout)[q] = make_float4(v[0], v[1], v[2], v[3]);
+                    for (int j = 0; j < NS; ++j)
+                        if (nrm && tid + 256 * j < aa.n_slots) ss += (double)sl[j];
+#pragma unroll
+                for (int j = 0; j < NPQ; ++j) {
+                    if (!nrm) break;
+                    float4 g = z4;
+#pragma unroll
+                    for (int b = 0; b < NRB; ++b) {
+                        if (b >= nrb_used) break;
+                        g.x += t[j][b].x;
+                        g.y += t[j][b].y;
+                        g.z += t[j][b].z;
+                        g.w += t[j][b].w;
+                    }
+                    if (4 * (tid + 256 * j) < n1) {
+                        reinterpret_cast<float4 *>(w1g)[tid + 256 * j] = g;
+                        if (fold) {
+                            ss += (double)g.x * (double)g.x;
+                            ss += (double)g.y * (double)g.y;
+                            ss += (double)g.z * (double)g.z;
+                            ss += (double)g.w * (double)g.w;
+                        }
+                    }
+                }
+                double tt[1] = {ss};
+                block_reduce<1>(tt, reinterpret_cast<double *>(red));   // its barriers also publish w1g
+                const float total = (float)sqrt(tt[0]) * aa.grad_scale;
+                coef = clip_coef(total, aa) * aa.grad_scale;
+                if (own1 && tid == 0 && af.metrics) af.metrics[kprev * GS_NUM_METRICS + GS_M_GRAD_NORM] = total;
+                if (own1 && tid == 0 && aa.normsq)
+                    aa.normsq[kprev] = tt[0] * (double)aa.grad_scale * (double)aa.grad_scale;
             }
-        }
-        auto step_slice = [&](float (&e)[4], int64_t o, bool own) {
-            if (o < 0 || !apply) return;
-            adam_param(e[3], coef, e[1], e[2], e[0], aa, neg_step, bc2s);
-            if (own) {
-                af.Pout[o] = e[0];
-                af.Mout[o] = e[1];
-                af.Vout[o] = e[2];
+            GS_STAMP(1)
+            // Adam on the owned parameters: new values to LDS / registers, and from row block 0 to the other set
+#pragma unroll
+            for (int j = 0; j < NQP; ++j) {
+                const int q = tid + NT * j;
+                if (4 * q >= n1) continue;
+                float4 p4 = w1p[j];
+                if (apply) {
+                    float p[4] = {p4.x, p4.y, p4.z, p4.w};
+                    float m[4] = {w1m[j].x, w1m[j].y, w1m[j].z, w1m[j].w};
+                    float v[4] = {w1v[j].x, w1v[j].y, w1v[j].z, w1v[j].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        adam_param(w1g[fold ? part1_index(Lc, 4 * q + e) : 4 * q + e], coef, m[e], v[e], p[e], aa,
+                                   neg_step, bc2s);
+                    p4 = make_float4(p[0], p[1], p[2], p[3]);
+                    // the new W1|b1 p / m / v are all stored by workgroup (0,0)
+                    if (stW1[0]) reinterpret_cast<float4 *>(af.Pout)[q] = p4;
+                    if (stW1[1]) reinterpret_cast<float4 *>(af.Mout)[q] = make_float4(m[0], m[1], m[2], m[3]);
+                    if (stW1[2]) reinterpret_cast<float4 *>(af.Vout)[q] = make_float4(v[0], v[1], v[2], v[3]);
+                }
+                reinterpret_cast<float4 *>(W1s)[q] = p4;
             }
+            if (apply) {
+#pragma unroll
+                for (int j = 0; j < kW2v; ++j) {
+                    const int u = tid + NT * j, i = u / k4n, k4 = u - i * k4n;
+                    if (c0 + i >= H2) continue;
+                    float p[4] = {w2r[j].x, w2r[j].y, w2r[j].z, w2r[j].w};
+                    float m[4] = {w2m[j].x, w2m[j].y, w2m[j].z, w2m[j].w};
+                    float v[4] = {w2v[j].x, w2v[j].y, w2v[j].z, w2v[j].w};
+                    const float g[4] = {w2g[j].x, w2g[j].y, w2g[j].z, w2g[j].w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) adam_param(g[e], coef, m[e], v[e], p[e], aa, neg_step, bc2s);
+                    w2r[j] = make_float4(p[0], p[1], p[2], p[3]);
+                    // this column block's 16 new W2 rows: p, m and v all by row block 0 (16 KB each)
+                    const int64_t q = (Lc.oW2 + (int64_t)(c0 + i) * cH1) / 4 + k4;
+                    if (stW2[0]) reinterpret_cast<float4 *>(af.Pout)[q] = w2r[j];
+                    if (stW2[1]) reinterpret_cast<float4 *>(af.Mout)[q] = make_float4(m[0], m[1], m[2], m[3]);
+                    if (stW2[2]) reinterpret_cast<float4 *>(af.Vout)[q] = make_float4(v[0], v[1], v[2], v[3]);
+                }
+            }
+            auto step_slice = [&](float (&e)[4], int64_t o, bool own) {
+                if (o < 0 || !apply) return;
+                adam_param(e[3], coef, e[1], e[2], e[0], aa, neg_step, bc2s);
+                if (own) {
+                    af.Pout[o] = e[0];
+                    af.Mout[o] = e[1];
+                    af.Vout[o] = e[2];
+                }
+            };
+            step_slice(sb, ob, own2);
+            step_slice(sw, ow, own2);
+            step_slice(shb, oh, own1);
+            if (tid < kTile) b2s[tid] = ob < 0 ? 0.0f : sb[0];
+            if (tid < cA1 * kTile) whs[tid] = ow < 0 ? 0.0f : sw[0];
+            if (tid < kTile * cD) xs[tid] = okx ? xv : 0.0f;
+            GS_STAMP(2)
         };
-        step_slice(sb, ob, own2);
-        step_slice(sw, ow, own2);
-        step_slice(shb, oh, own1);
-        if (tid < kTile) b2s[tid] = ob < 0 ? 0.0f : sb[0];
-        if (tid < cA1 * kTile) whs[tid] = ow < 0 ? 0.0f : sw[0];
-        if (tid < kTile * cD) xs[tid] = okx ? xv : 0.0f;
-        GS_STAMP(2)
+        for_wave_class<WC, 0>(__builtin_amdgcn_readfirstlane(wave), prologue);
     } else if constexpr (kStage0) {
         constexpr Layout Lc = S::lay(Layout{});
         constexpr int cD = Lc.D, cH1 = Lc.H1, cA1 = Lc.A + 1;
