@@ -304,6 +304,12 @@ struct DynEnvArgs {
     uint64_t seed;
     int64_t env_offset;
 };
+// MountainCar (GS_ENV_MOUNTAINCAR, obs dim 2, 3 actions): the same tensors plus the count tables
+// [N][position_bins * velocity_bins] (HBM; null without a count bonus) and the wrappers
+struct MountainCarEnvArgs : DynEnvArgs {
+    int32_t *counts;
+    gs_mountaincar_wrappers w;
+};
 
 bool rollout_synth_fits(const Layout &L);
 int launch_rollout_synth(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
@@ -311,6 +317,11 @@ int launch_rollout_synth(const float *P, const Layout &L, int64_t N, int T, int 
 bool rollout_env_fits(const Layout &L, int kind);
 int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
                        uint64_t counter0, int kind, const DynEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
+// null, or what is wrong with the wrappers (their order, the bonus' table and parameters): every
+// MountainCar entry checks this before a launch, so no index leaves an env's table (gs_mountaincar.hip)
+const char *mountaincar_wrappers_error(const gs_mountaincar_wrappers &w, const void *counts);
+int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                               uint64_t counter0, const MountainCarEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
 
 inline int n_col_blocks(int H) { return (H + kTile - 1) / kTile; }
 inline int n_sumsq_slots(const Layout &L) { return n_col_blocks(L.H2) * n_col_blocks(L.H1) + 2 * n_col_blocks(L.H2) + 1; }

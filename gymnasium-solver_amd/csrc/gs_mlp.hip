@@ -44,6 +44,7 @@
 #include "gs_synth_env.h"
 #include "gs_cartpole_env.h"
 #include "gs_acrobot_env.h"
+#include "gs_mountaincar_env.h"
 
 namespace gs {
 
@@ -1246,7 +1247,7 @@ __global__ __launch_bounds__(256) void k_heads_act(const float *__restrict__ P, 
 
 // ------------------------------------------------------------------------------------
 // k_rollout_env: a whole rollout of a device env in one launch (C3-sized MLPs, whose
-// weights fit in LDS), generic over the env E: the synthetic env, CartPole or Acrobot.  Workgroup = 16 envs (one MFMA row tile) for all T vector steps: the
+// weights fit in LDS), generic over the env E: the synthetic env, CartPole, Acrobot or MountainCar.  Workgroup = 16 envs (one MFMA row tile) for all T vector steps: the
 // policy's act with gs_policy_act's arithmetic in its order (h1 fmaf chain + bias; each h2
 // column block's 4 K-range MFMA partials summed in range order, as the 4 waves of
 // k_fwd_hidden do; partial heads per column block summed in block order as k_heads_act), so the
@@ -1345,6 +1346,26 @@ struct RolloutAcrobotEnv : RolloutDynEnvBase<ACState, 6> {
                                              bool env_thread) const
     {
         if (env_thread) acrobot_write_obs(s, xs + 6 * tid);
+    }
+};
+
+// MountainCar: its own Args (the count tables and the wrappers ride behind DynEnvArgs), so the
+// other instantiations' kernel arguments stay where they are.  The tables stay in HBM: thread
+// `me` reads and bumps one cell of env me's table per step.
+struct RolloutMountainCarEnv : RolloutDynEnvBase<MCState, 2> {
+    using Args = MountainCarEnvArgs;
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        int32_t *table = ev.counts ? ev.counts + me * ((int64_t)ev.w.position_bins * ev.w.velocity_bins) : nullptr;
+        return mountaincar_env_step(s, meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me), ev.w,
+                                    table, ev.ep_cnt ? ev.ep_cnt + me : nullptr,
+                                    ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
+                                    ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+    }
+    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
+                                             bool env_thread) const
+    {
+        if (env_thread) mountaincar_write_obs(s, xs + 2 * tid);
     }
 };
 
@@ -1565,6 +1586,7 @@ bool rollout_env_fits(const Layout &L, int kind)
 {
     if (kind == GS_ENV_CARTPOLE) return L.D == 4 && L.A == 2 && rollout_synth_fits(L);
     if (kind == GS_ENV_ACROBOT) return L.D == 6 && L.A == 3 && rollout_synth_fits(L);
+    if (kind == GS_ENV_MOUNTAINCAR) return L.D == 2 && L.A == 3 && rollout_synth_fits(L);
     return false;
 }
 
@@ -1577,6 +1599,14 @@ int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mo
     if (kind == GS_ENV_CARTPOLE)
         return launch_rollout_sh<ShapeR<4>, RolloutCartPoleEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
     return launch_rollout_sh<ShapeR<4>, RolloutAcrobotEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
+}
+
+int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                               uint64_t counter0, const MountainCarEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
+{
+    GS_REQUIRE(rollout_env_fits(L, GS_ENV_MOUNTAINCAR),
+               "gs_rollout_mountaincar: the policy is not MountainCar's (obs dim 2, 3 actions) or does not fit in LDS");
+    return launch_rollout_sh<ShapeR<4>, RolloutMountainCarEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
 }
 
 // ------------------------------------------------------------------------------------

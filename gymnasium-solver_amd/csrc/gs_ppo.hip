@@ -168,6 +168,8 @@ extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, 
     if (rc) return rc;
     GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_env: bad N / T");
     GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_env: mode %d not in {0,1,2}", mode);
+    GS_REQUIRE(kind != GS_ENV_MOUNTAINCAR,
+               "gs_rollout_env: MountainCar takes its count tables and wrappers through gs_rollout_mountaincar");
     GS_REQUIRE(kind == GS_ENV_CARTPOLE || kind == GS_ENV_ACROBOT,
                "gs_rollout_env: env kind %d has no dynamics here (the synthetic env: gs_rollout_synth)", kind);
     GS_REQUIRE(max_steps > 0, "gs_rollout_env: max_steps must be > 0");
@@ -180,6 +182,34 @@ extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, 
     RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
     return launch_rollout_env(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, kind, ev, rw,
                               (hipStream_t)stream);
+}
+
+extern "C" int gs_rollout_mountaincar(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                      uint64_t rng_seed, uint64_t rng_counter0, double *env_state, int32_t *env_meta,
+                                      float *env_ep_ret, float *env_obs, int32_t *env_counts,
+                                      gs_mountaincar_wrappers wrappers, int32_t max_steps, uint64_t env_seed,
+                                      int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum,
+                                      float *ep_len_sum, float *obs_rows, int64_t *action_rows, float *logp_rows,
+                                      float *value_rows, float *reward_rows, uint8_t *done_rows,
+                                      uint8_t *timeout_rows, void *stream)
+{
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_mountaincar: bad N / T");
+    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_mountaincar: mode %d not in {0,1,2}", mode);
+    GS_REQUIRE(max_steps > 0, "gs_rollout_mountaincar: max_steps must be > 0");
+    GS_REQUIRE(params && env_state && env_meta && env_ep_ret && env_obs && obs_rows && action_rows && logp_rows &&
+                   value_rows && reward_rows && done_rows && timeout_rows,
+               "gs_rollout_mountaincar: null buffer");
+    const char *bad = mountaincar_wrappers_error(wrappers, env_counts);
+    GS_REQUIRE(!bad, "gs_rollout_mountaincar: %s", bad);
+    if (T == 0) return GS_OK;
+    MountainCarEnvArgs ev{{env_state, env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
+                           env_seed, env_offset},
+                          env_counts, wrappers};
+    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return launch_rollout_mountaincar(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
+                                      (hipStream_t)stream);
 }
 
 extern "C" int gs_policy_value(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, float *value,

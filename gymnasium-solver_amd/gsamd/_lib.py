@@ -19,6 +19,9 @@ GS_OK, GS_E_INVALID, GS_E_HIP, GS_E_COMM = 0, -1, -2, -3
 GS_ABI_VERSION = 7          # include/gsamd.h: the argument lists this binding declares
 GS_NUM_METRICS = 40
 GS_ENV_SYNTHETIC, GS_ENV_CARTPOLE, GS_ENV_ACROBOT = 0, 1, 2     # include/gsamd.h: gs_rollout_env kinds
+GS_ENV_MOUNTAINCAR = 3      # answered by gs_rollout_env_supported; rolled out by gs_rollout_mountaincar
+GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER, GS_MC_WRAP_BONUS = 0, 1, 2
+GS_MC_BONUS_TYPES = {"count": 0, "inverse": 1, "log": 2}       # GS_MC_BONUS_*
 METRIC_SLOTS = (
     "loss", "policy_loss", "value_loss", "entropy", "clip_fraction", "clip_fraction_vf",
     "explained_var", "kl", "approx_kl", "adv_norm_mean", "adv_norm_std", "kl_stop", "grad_norm",
@@ -35,6 +38,14 @@ M = {name: i for i, name in enumerate(METRIC_SLOTS)}
 class MlpDims(ctypes.Structure):
     _fields_ = [("obs_dim", ctypes.c_int32), ("hidden1", ctypes.c_int32), ("hidden2", ctypes.c_int32),
                 ("n_actions", ctypes.c_int32)]
+
+
+class MountainCarWrappers(ctypes.Structure):
+    """gs_mountaincar_wrappers (include/gsamd.h): up to two wrappers, innermost first."""
+    _fields_ = [("order", ctypes.c_int32 * 2), ("position_reward_scale", ctypes.c_double),
+                ("velocity_reward_scale", ctypes.c_double), ("height_reward_scale", ctypes.c_double),
+                ("position_bins", ctypes.c_int32), ("velocity_bins", ctypes.c_int32),
+                ("bonus_type", ctypes.c_int32), ("min_count", ctypes.c_int32), ("bonus_scale", ctypes.c_double)]
 
 
 class PPOHparams(ctypes.Structure):
@@ -136,6 +147,12 @@ def _load():
         "gs_cartpole_step": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
         "gs_acrobot_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, u64, i64, vp]),
         "gs_acrobot_step": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_mountaincar_reset": (ctypes.c_int, [vp, vp, vp, vp, vp, MountainCarWrappers, i64, u64, i64, vp]),
+        "gs_mountaincar_step": (ctypes.c_int, [vp, vp, vp, vp, vp, MountainCarWrappers, vp, i64, i32, u64, i64, vp, vp,
+                                               vp, vp, vp, vp, vp]),
+        "gs_rollout_mountaincar": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
+                                                  MountainCarWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                  vp, vp, vp]),
         "gs_atari_preprocess": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),
         "gs_atari_render": (ctypes.c_int, [vp, i64, u64, i64, u64, vp]),
         "gs_atari_env_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, u64, i64, vp]),
@@ -178,7 +195,8 @@ EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_norma
             "gs_ppo_graph_cache_info", "gs_ppo_exchange_inside_bwd",
             "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
             "gs_cnn_ppo_update_global",
-            "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
+            "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",
+            "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
             "gs_comm_init", "gs_comm_xgmi_create", "gs_comm_xgmi_connect", "gs_comm_status", "gs_comm_error_record",
             "gs_comm_xgmi_set_colocation", "gs_comm_xgmi_set_bwd_exchange", "gs_comm_xgmi_reset",
             "gs_comm_allreduce_mean_f32", "gs_comm_allreduce_sum_f64", "gs_ppo_global_adv_stats",

@@ -68,12 +68,13 @@ class PPOConfig:
     episode_len: int = 200
     truncate_every: int = 0
     # which env the agent steps when the caller passes none (device_env_kind):
-    #   "auto"      the env_id's own dynamics where the device implements them (CartPole-v1, Acrobot-v1),
-    #               otherwise the caller must pass the host VectorEnv (raises if not)
+    #   "auto"      the env_id's own dynamics where the device implements them (CartPole-v1, Acrobot-v1,
+    #               MountainCar-v0), otherwise the caller must pass the host VectorEnv (raises if not)
     #   "synthetic" the fixed-length-episode synthetic env of SURVEY §8d (bench / tests), or the
     #               synthetic Atari frame source for rgb configs
     #   "cartpole"  device CartPole-v1 dynamics
     #   "acrobot"   device Acrobot-v1 dynamics
+    #   "mountaincar" device MountainCar-v0 dynamics with the config's env_wrappers
     env_dynamics: str = "auto"
     # data-parallel semantics of a multi-rank update:
     #   "local"  every rank takes B-row minibatches of its own samples (weak scaling, global batch G·B)
@@ -182,24 +183,88 @@ class PPOConfig:
 _FIELDS = {f.name for f in dataclasses.fields(PPOConfig)}
 _ALIASES = {"LunarLander-v2": "LunarLander-v3"}
 
-ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot")
+ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot", "mountaincar")
 # env ids whose dynamics the device implements, as BaseAgent.build_env would build them from a
 # config without wrappers / env kwargs / observation normalisation
-DEVICE_DYNAMICS = {"CartPole-v1": "cartpole", "Acrobot-v1": "acrobot"}
+DEVICE_DYNAMICS = {"CartPole-v1": "cartpole", "Acrobot-v1": "acrobot", "MountainCar-v0": "mountaincar"}
+
+# The env_wrappers the device MountainCar-v0 applies itself (csrc/gs_mountaincar_env.h), with the
+# keyword arguments and defaults of the reference's classes
+# (gym_wrappers/MountainCarV0/reward_shaper.py:9, state_count_bonus.py:13-21)
+MOUNTAINCAR_WRAPPERS = {
+    "MountainCarV0_RewardShaper": {"position_reward_scale": 100.0, "velocity_reward_scale": 10.0,
+                                   "height_reward_scale": 50.0},
+    "MountainCarV0_StateCountBonus": {"position_bins": 50, "velocity_bins": 50, "bonus_scale": 1.0,
+                                      "bonus_type": "count", "min_count": 1},
+}
+MOUNTAINCAR_BONUS_TYPES = ("count", "inverse", "log")
+MOUNTAINCAR_MAX_CELLS = 16384      # position_bins * velocity_bins of one env's count table
+
+
+def _is_int(v) -> bool:
+    return isinstance(v, int) and not isinstance(v, bool)
+
+
+def _is_real(v) -> bool:
+    return isinstance(v, (int, float)) and not isinstance(v, bool) and v == v and abs(v) != float("inf")
+
+
+def resolve_mountaincar_wrappers(wrappers) -> Optional[List[Tuple[str, Dict[str, Any]]]]:
+    """A config's env_wrappers list as [(id, keyword arguments with the reference's defaults
+    filled in)], in list order (first entry innermost), when the device MountainCar applies it:
+    each entry one of MOUNTAINCAR_WRAPPERS, each id at most once, only the classes' own keyword
+    arguments, bonus_type one of count / inverse / log, min_count an integer >= 1, positive
+    integer bins with position_bins * velocity_bins <= 16384.  None for any other list (the
+    host env then)."""
+    out, seen = [], set()
+    for w in wrappers or []:
+        if not isinstance(w, dict):
+            return None
+        wid = w.get("id")
+        if wid not in MOUNTAINCAR_WRAPPERS or wid in seen:
+            return None
+        seen.add(wid)
+        kw = dict(MOUNTAINCAR_WRAPPERS[wid])
+        for k, v in w.items():
+            if k == "id":
+                continue
+            if k not in kw:
+                return None
+            kw[k] = v
+        if wid == "MountainCarV0_RewardShaper":
+            if not all(_is_real(v) for v in kw.values()):
+                return None
+        else:
+            pb, vb = kw["position_bins"], kw["velocity_bins"]
+            if not (_is_int(pb) and _is_int(vb) and pb > 0 and vb > 0 and pb * vb <= MOUNTAINCAR_MAX_CELLS):
+                return None
+            if kw["bonus_type"] not in MOUNTAINCAR_BONUS_TYPES or not _is_real(kw["bonus_scale"]):
+                return None
+            if not (_is_int(kw["min_count"]) and kw["min_count"] >= 1):
+                return None
+        out.append((wid, kw))
+    return out
 
 
 def device_env_kind(cfg) -> Optional[str]:
     """The device env a config trains on when the caller passes no env: "synthetic",
-    "cartpole", "acrobot", or None when the config names an env the device does not simulate — the
-    caller then passes the host VectorEnv the reference would build
-    (agents/base_agent.py:129-192 → utils/environment.py:421-425 build_env_from_config)."""
+    "cartpole", "acrobot", "mountaincar", or None when the config names an env the device does not
+    simulate — the caller then passes the host VectorEnv the reference would build
+    (agents/base_agent.py:129-192 → utils/environment.py:421-425 build_env_from_config).
+    MountainCar-v0 may carry the env_wrappers the device applies itself
+    (resolve_mountaincar_wrappers); any wrapper on another env means the host env."""
     mode = str(getattr(cfg, "env_dynamics", None) or "auto")
     if mode != "auto":
         return mode
     if str(getattr(cfg, "obs_type", "vector")) == "rgb":
         return None
     kind = DEVICE_DYNAMICS.get(str(getattr(cfg, "env_id", "")))
-    plain = (not getattr(cfg, "env_wrappers", None) and not getattr(cfg, "env_kwargs", None)
+    wrappers = getattr(cfg, "env_wrappers", None)
+    if kind == "mountaincar":
+        unwrapped = resolve_mountaincar_wrappers(wrappers) is not None
+    else:
+        unwrapped = not wrappers
+    plain = (unwrapped and not getattr(cfg, "env_kwargs", None)
              and not getattr(cfg, "normalize_obs", False) and getattr(cfg, "frame_stack", None) in (None, 0, 1))
     return kind if plain else None
 

@@ -29,7 +29,8 @@ from .atari_env import DeviceAtariVecEnv
 from .config import device_env_kind
 from .cnn import DeviceCNNActorCritic
 from .policy import DeviceMLPActorCritic
-from .rollout import DeviceAcrobotVecEnv, DeviceCartPoleVecEnv, DeviceRolloutCollector, DeviceSyntheticVecEnv
+from .rollout import (DeviceAcrobotVecEnv, DeviceCartPoleVecEnv, DeviceMountainCarVecEnv, DeviceRolloutCollector,
+                      DeviceSyntheticVecEnv)
 from .samplers import IndexStreamPrefetcher, MultiPassRandomSampler, index_stream, rank_share
 from .distributed import allreduce_sum_f64, broadcast_int, check_replicas, comm_status, world_active
 from . import distributed as _dist
@@ -121,6 +122,13 @@ class DevicePPOAgent:
                 raise ValueError("env_dynamics='acrobot' needs vector observations of dim 6 and 3 actions")
             return DeviceAcrobotVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
                                        max_steps=int(c.max_episode_steps or 500), device=self.device)
+        if kind == "mountaincar":
+            if self.is_pixel or c.resolved_obs_dim() != 2 or c.resolved_n_actions() != 3:
+                raise ValueError("env_dynamics='mountaincar' needs vector observations of dim 2 and 3 actions")
+            # every stage's env carries the config's wrappers (the reference builds each from the same list)
+            return DeviceMountainCarVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
+                                           max_steps=int(c.max_episode_steps or 200),
+                                           wrappers=list(c.env_wrappers or ()), device=self.device)
         seed = c.seed if train else c.seed + 1000
         if self.is_pixel:
             return DeviceAtariVecEnv(n_envs=c.n_envs, n_actions=c.resolved_n_actions(), episode_len=c.episode_len,
@@ -774,8 +782,8 @@ class DevicePPOAgent:
 def build_agent(config, *args, **kwargs):
     """agents/__init__.py:1-8 for the device path.  Accepts a gsamd PPOConfig or the
     reference's own Config object (adapted by name, gsamd.config.from_reference_config).
-    The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1 and Acrobot-v1 step on
-    their device dynamics; any other env_id needs env= / env_factory= (the host VectorEnv
+    The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1, Acrobot-v1 and
+    MountainCar-v0 (with its reward shaper / state-count bonus wrappers) step on their device dynamics; any other env_id needs env= / env_factory= (the host VectorEnv
     the reference's build_env_from_config returns); the synthetic env only with
     env_dynamics='synthetic'."""
     from .config import from_reference_config

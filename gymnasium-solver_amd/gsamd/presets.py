@@ -2,9 +2,11 @@
 
 PRESETS holds what the reference's load_config(...) resolves for each id (values taken
 from config/environments/{CartPole-v1,LunarLander-v3,Acrobot-v1,ALE-Pong-v5,ALE-Breakout-v5}.yaml
-through utils/config.py; tests/golden/configs.json, and config_acrobot.json for Acrobot-v1:ppo, are
-the machine-generated records the tests compare against).  MODEL_REGISTRY mirrors
-utils/model_registry.py:17-76.
+through utils/config.py; tests/golden/configs.json, config_acrobot.json for Acrobot-v1:ppo and
+config_mountaincar.json for the three MountainCar-v0 variants are the machine-generated records
+the tests compare against).  The reference leaves MountainCar-v0's n_envs at "auto", the host's core
+count (utils/config.py:482-485): the record keeps "auto" and the presets take 32.  MODEL_REGISTRY
+mirrors utils/model_registry.py:17-76.
 """
 
 MODEL_REGISTRY = {
@@ -22,6 +24,11 @@ MODEL_REGISTRY = {
 
 _COMMON = dict(algo_id="ppo", clip_range_vf=0.2, vf_coef=0.5, max_grad_norm=0.5, normalize_advantages="batch",
                seed=42, target_kl=None, optimizer="adam")
+
+_MC_SHAPER = dict(id="MountainCarV0_RewardShaper", position_reward_scale=100.0, velocity_reward_scale=10.0,
+                  height_reward_scale=50.0)
+_MC_CURIOSITY = dict(id="MountainCarV0_StateCountBonus", position_bins=50, velocity_bins=50, bonus_scale=0.1,
+                     bonus_type="count")
 
 PRESETS = {
     "CartPole-v1:ppo": dict(
@@ -42,6 +49,17 @@ PRESETS = {
         model_id="mlp_small", max_env_steps=1000000.0, obs_type="vector", accelerator="cpu",
         spec={"action_space": {"discrete": 3}, "observation_space": {"default": "state",
                                                                      "variants": {"state": {"shape": [6]}}}}),
+    **{f"MountainCar-v0:{variant}": dict(
+        _COMMON, env_id="MountainCar-v0", project_id=project, n_envs=32, n_steps=2048, batch_size=64,
+        n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, policy_lr=0.0003,
+        model_id="mlp_medium", max_env_steps=None, obs_type="vector", accelerator="cpu", env_wrappers=wrappers,
+        spec={"action_space": {"discrete": 3}, "observation_space": {"default": "state",
+                                                                     "variants": {"state": {"shape": [2]}}}})
+       for variant, project, wrappers in (
+           # `ppo` is the curiosity env too (config/environments/MountainCar-v0.yaml:74-77)
+           ("ppo", "MountainCar-v0_curiosity", [dict(_MC_CURIOSITY)]),
+           ("ppo_rewardshaped", "MountainCar-v0_rewardshaped", [dict(_MC_SHAPER)]),
+           ("ppo_curiosity", "MountainCar-v0_curiosity", [dict(_MC_CURIOSITY)]))},
     "ALE-Pong-v5:rgb_ppo": dict(
         _COMMON, env_id="ALE/Pong-v5", project_id="ALE-Pong-v5_rgb", n_envs=32, n_steps=256, batch_size=1024,
         n_epochs=15, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.01, policy_lr=0.0003,

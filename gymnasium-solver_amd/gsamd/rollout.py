@@ -30,7 +30,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import GS_ENV_ACROBOT, GS_ENV_CARTPOLE, check, lib, ptr, stream_handle
+from ._lib import (GS_ENV_ACROBOT, GS_ENV_CARTPOLE, GS_ENV_MOUNTAINCAR, GS_MC_BONUS_TYPES, GS_MC_WRAP_BONUS,
+                   GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER, MountainCarWrappers, check, lib, ptr, stream_handle)
+from .config import resolve_mountaincar_wrappers
 from .distributed import allreduce_sum_f64
 from .rollout_stats import RollingWindow
 
@@ -147,6 +149,83 @@ class DeviceAcrobotVecEnv:
                                   self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
                                   ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
                                   ptr(self.ep_len_sum), stream_handle()), "gs_acrobot_step")
+
+
+def mountaincar_wrappers_struct(wrappers) -> MountainCarWrappers:
+    """An env_wrappers list (config form: [{"id": ..., **kwargs}], first entry innermost) as the
+    gs_mountaincar_wrappers the kernels take; ValueError for a list the device does not apply."""
+    resolved = resolve_mountaincar_wrappers(list(wrappers or ()))
+    if resolved is None or len(resolved) > 2:
+        raise ValueError(f"the device MountainCar-v0 does not apply env_wrappers={list(wrappers)!r} "
+                         "(gsamd.config.resolve_mountaincar_wrappers)")
+    w = MountainCarWrappers()
+    w.order[0] = w.order[1] = GS_MC_WRAP_NONE
+    for i, (wid, kw) in enumerate(resolved):
+        if wid == "MountainCarV0_RewardShaper":
+            w.order[i] = GS_MC_WRAP_SHAPER
+            w.position_reward_scale = float(kw["position_reward_scale"])
+            w.velocity_reward_scale = float(kw["velocity_reward_scale"])
+            w.height_reward_scale = float(kw["height_reward_scale"])
+        else:
+            w.order[i] = GS_MC_WRAP_BONUS
+            w.position_bins, w.velocity_bins = int(kw["position_bins"]), int(kw["velocity_bins"])
+            w.bonus_type, w.min_count = GS_MC_BONUS_TYPES[kw["bonus_type"]], int(kw["min_count"])
+            w.bonus_scale = float(kw["bonus_scale"])
+    return w
+
+
+class DeviceMountainCarVecEnv:
+    """MountainCar-v0 on device with the reference's reward shaper / state-count bonus wrappers
+    (csrc/gs_mountaincar_env.h: gymnasium 1.x dynamics in double precision,
+    NEXT_STEP autoreset, TimeLimit 200; the wrappers in double on the float32 observation, in list
+    order).  `wrappers` is the config's env_wrappers list.  `counts` holds one int32 visit table
+    per env, (N, position_bins * velocity_bins), (N, 0) without a count bonus; reset() zeroes it,
+    an episode boundary does not.  Parity with gymnasium's own episodes is unpinned (reset draws
+    use a counter hash, not PCG64); the wrappers' arithmetic is pinned to the reference's classes
+    (tests/golden/mountaincar_wrappers.npz).  The wrappers' info diagnostics are not reproduced."""
+
+    device_native = True
+    env_kind = GS_ENV_MOUNTAINCAR
+    # One-launch rollouts are the default only up to this many envs: past it the graph-replayed
+    # step loop measured faster (DESIGN.md §4.1, profiles/mountaincar_collect.json).  None = always.
+    one_launch_max_envs = None
+
+    def __init__(self, n_envs, seed=42, env_offset=0, max_steps=200, wrappers=(), device="cuda", **_):
+        self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 2, 3
+        self.seed, self.env_offset, self.max_steps = int(seed), int(env_offset), int(max_steps)
+        self.obs_shape, self.obs_dtype = (2,), torch.float32
+        self.device = torch.device(device)
+        self.wrappers = [dict(w) for w in (wrappers or ())]
+        self.wrappers_c = mountaincar_wrappers_struct(self.wrappers)
+        cells = self.wrappers_c.position_bins * self.wrappers_c.velocity_bins \
+            if GS_MC_WRAP_BONUS in tuple(self.wrappers_c.order) else 0
+        N, z = self.num_envs, dict(device=self.device)
+        self.state = torch.zeros(N, 4, dtype=torch.float64, **z)      # p, v, prev obs p, prev obs v
+        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
+        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
+        self.obs = torch.zeros(N, 2, dtype=torch.float32, **z)
+        self.counts = torch.zeros(N, cells, dtype=torch.int32, **z)
+        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
+        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
+        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
+
+    def _counts_ptr(self):
+        return ptr(self.counts) if self.counts.numel() else None
+
+    def reset(self):
+        check(lib.gs_mountaincar_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs),
+                                       self._counts_ptr(), self.wrappers_c, self.num_envs, self.seed,
+                                       self.env_offset, stream_handle()), "gs_mountaincar_reset")
+        return self.obs, {}
+
+    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
+        if actions is None:
+            raise ValueError("MountainCar dynamics need the step's actions")
+        check(lib.gs_mountaincar_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs),
+                                      self._counts_ptr(), self.wrappers_c, ptr(actions), self.num_envs,
+                                      self.max_steps, self.seed, self.env_offset, ptr(rewards_row), ptr(dones_row),
+                                      ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
+                                      ptr(self.ep_len_sum), stream_handle()), "gs_mountaincar_step")
 
 
 class DeviceRolloutBuffer:
@@ -420,6 +499,14 @@ class DeviceRolloutCollector:
         LDS): gs_rollout_env for an env with real dynamics, else gs_rollout_synth, after which
         the synthetic env's host step counter advances by T."""
         buf, pm, env = self._buffer, self.policy_model, self.env
+        if isinstance(env, DeviceMountainCarVecEnv):     # its count tables and wrappers ride along
+            check(lib.gs_rollout_mountaincar(
+                ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed, self.total_vec_steps,
+                ptr(env.state), ptr(env.meta), ptr(env.ep_ret), ptr(env.obs), env._counts_ptr(), env.wrappers_c,
+                env.max_steps, env.seed, env.env_offset, ptr(env.ep_count), ptr(env.ep_ret_sum),
+                ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values),
+                ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_mountaincar")
+            return
         if not isinstance(env, DeviceSyntheticVecEnv):
             check(lib.gs_rollout_env(ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed,
                                      self.total_vec_steps, int(env.env_kind), ptr(env.state), ptr(env.meta),

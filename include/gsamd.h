@@ -141,7 +141,8 @@ int gs_rollout_synth(const float *params_dev, gs_mlp_dims dims, int64_t N, int64
 /* The same one-launch rollout on a device env with real dynamics: kind GS_ENV_CARTPOLE
  * (gs_cartpole_*: obs dim 4, 2 actions) or GS_ENV_ACROBOT (gs_acrobot_*: obs dim 6, 3 actions).
  * gs_rollout_env_supported: *supported_host = 1 when dims are that env's and the policy fits in
- * LDS (kind GS_ENV_SYNTHETIC answers as gs_rollout_synth_supported).  gs_rollout_env: env_state_dev
+ * LDS (kind GS_ENV_SYNTHETIC answers as gs_rollout_synth_supported, kind GS_ENV_MOUNTAINCAR for
+ * gs_rollout_mountaincar: obs dim 2, 3 actions; gs_rollout_env itself refuses that kind).  gs_rollout_env: env_state_dev
  * / env_meta_dev / env_ep_ret_dev / env_obs_dev and the episode counters are the env's tensors as
  * its gs_*_step takes them; every row, the final env state / meta / observations and the episode
  * counters equal T calls of gs_policy_act + the env's gs_*_step bit for bit, in all three modes
@@ -150,6 +151,7 @@ int gs_rollout_synth(const float *params_dev, gs_mlp_dims dims, int64_t N, int64
 #define GS_ENV_SYNTHETIC 0
 #define GS_ENV_CARTPOLE 1
 #define GS_ENV_ACROBOT 2
+#define GS_ENV_MOUNTAINCAR 3   /* answered by gs_rollout_env_supported; its rollout entry is gs_rollout_mountaincar */
 int gs_rollout_env_supported(gs_mlp_dims dims, int kind, int *supported_host);
 int gs_rollout_env(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
                    uint64_t rng_counter0, int kind, double *env_state_dev, int32_t *env_meta_dev,
@@ -490,6 +492,55 @@ int gs_acrobot_step(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, flo
                     const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed, int64_t env_offset,
                     float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
                     int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
+
+/* ---------------------------------------------------------------- MountainCar-v0 dynamics (f1)
+ * gymnasium 1.x MountainCarEnv.step restated on device, with the reference's two MountainCar
+ * reward wrappers (gym_wrappers/MountainCarV0/reward_shaper.py, state_count_bonus.py) applied on
+ * the env's own thread.  state_dev: (N, 4) f64 {position, velocity, prev_position, prev_velocity}
+ * (prev_*: the float32 observation the shaper last saw).  Double precision: v += (a - 1) 0.001 +
+ * cos(3 p) (-0.0025), v clipped to +-0.07, p += v, p clipped to [-1.2, 0.6], v = 0 at the left
+ * wall; terminated when p >= 0.5 and v >= 0; reward -1 on every step; TimeLimit max_steps;
+ * NEXT_STEP autoreset (the reset step adds no wrapper term).  obs_dev: (N, 2) f32.  Reset: p
+ * uniform in [-0.6, -0.4) from the counter hash (kept in double), v = 0; gymnasium's PCG64 stream
+ * is not reproduced (parity with gymnasium's own episodes is unpinned).
+ * Wrappers (gs_mountaincar_wrappers, by value): order[] lists up to two of GS_MC_WRAP_SHAPER /
+ * GS_MC_WRAP_BONUS, innermost first, each at most once, GS_MC_WRAP_NONE in the unused slots; they
+ * work in double on the float32 observation and the step's reward is (float)(-1 + addends in
+ * that order).  The count bonus reads and increments counts_dev: (N, position_bins *
+ * velocity_bins) i32, env e's row only by env e's thread (no atomics); gs_mountaincar_reset
+ * zeroes it, an episode boundary does not.  counts_dev may be null without a count bonus.
+ * meta_dev / actions_dev / rows / counters as gs_cartpole_step. */
+#define GS_MC_WRAP_NONE 0
+#define GS_MC_WRAP_SHAPER 1
+#define GS_MC_WRAP_BONUS 2
+#define GS_MC_BONUS_COUNT 0     /* scale / sqrt(max(count, min_count)) */
+#define GS_MC_BONUS_INVERSE 1   /* scale / max(count, min_count) */
+#define GS_MC_BONUS_LOG 2       /* scale / log(max(count, min_count) + 1) */
+typedef struct gs_mountaincar_wrappers {
+    int32_t order[2];
+    double position_reward_scale, velocity_reward_scale, height_reward_scale;
+    int32_t position_bins, velocity_bins;      /* > 0, product <= 16384 */
+    int32_t bonus_type, min_count;             /* GS_MC_BONUS_*, >= 1 */
+    double bonus_scale;
+} gs_mountaincar_wrappers;
+int gs_mountaincar_reset(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, int32_t *counts_dev,
+                         gs_mountaincar_wrappers wrappers, int64_t N, uint64_t seed, int64_t env_offset, void *stream);
+int gs_mountaincar_step(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, int32_t *counts_dev,
+                        gs_mountaincar_wrappers wrappers, const int64_t *actions_dev, int64_t N, int32_t max_steps,
+                        uint64_t seed, int64_t env_offset, float *rewards_row_dev, uint8_t *dones_row_dev,
+                        uint8_t *timeouts_row_dev, int32_t *ep_done_count_dev, float *ep_ret_sum_dev,
+                        float *ep_len_sum_dev, void *stream);
+/* gs_rollout_env for MountainCar (kind GS_ENV_MOUNTAINCAR: obs dim 2, 3 actions): the same
+ * one-launch rollout with the env's count tables and wrappers; the tables stay in HBM (L2), the
+ * kernel's LDS budget is gs_rollout_env's.  Bit for bit T calls of gs_policy_act +
+ * gs_mountaincar_step, counts included. */
+int gs_rollout_mountaincar(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                           uint64_t rng_seed, uint64_t rng_counter0, double *env_state_dev, int32_t *env_meta_dev,
+                           float *env_ep_ret_dev, float *env_obs_dev, int32_t *env_counts_dev,
+                           gs_mountaincar_wrappers wrappers, int32_t max_steps, uint64_t env_seed, int64_t env_offset,
+                           int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev,
+                           float *obs_rows_dev, int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev,
+                           float *reward_rows_dev, uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
 
 /* The fp32 MFMA GEMM under the CNN path (convolutions as GEMMs, fc, heads), exported for its
  * tests: row-major C[M][N] = op(A) op(B) + beta C (+ bias[n]) (ReLU if relu), op(X) = X^T

@@ -9,6 +9,11 @@ for `rocprofv3 --kernel-trace --stats`.
         arms in one process, alternated, `--warmup` rollouts per arm first (the graph is captured
         on the second), then `--repeats` timed blocks of `rollouts` rollouts per arm.
 
+  python tools/collect_run.py --env MountainCar-v0 --variant ppo_curiosity --override model_id=mlp_small \
+        --override env_wrappers=[] ...
+        `--override K=V` (repeatable) sets a config field after resolution, as train.py's option
+        does; V is read as JSON where it parses (numbers, lists, null), else as a string.
+
 Prints the mean collect time per rollout from HIP events on the launch stream."""
 import argparse
 import json
@@ -43,7 +48,8 @@ def _timed(coll, n):
 
 
 def _ab(a, env_id, over):
-    out = {"env": f"{env_id}:{a.variant}", "rollouts_per_block": a.rollouts, "warmup_rollouts": a.warmup,
+    out = {"env": f"{env_id}:{a.variant}", "overrides": {k: v for k, v in over.items() if k != "n_envs"},
+           "rollouts_per_block": a.rollouts, "warmup_rollouts": a.warmup,
            "arms": {"one_launch": "gs_rollout_env, one launch per rollout",
                     "graph": "captured step loop (gs_policy_act + env step per vector step), one replay per rollout"},
            "unit": "ms per rollout (collect: rollout + last value + GAE + episode window), HIP events", "results": []}
@@ -88,6 +94,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--repeats", type=int, default=2)
     ap.add_argument("--json", default=None, help="--ab: write the record here")
+    ap.add_argument("--override", action="append", default=[], metavar="K=V",
+                    help="set config field K to V after resolution (V as JSON where it parses); repeatable")
     a = ap.parse_args()
     if a.workload is not None and a.workload.isdigit() and a.rollouts is None:      # --env ... [rollouts]
         a.workload, a.rollouts = None, int(a.workload)
@@ -98,6 +106,14 @@ def main():
         tag = a.workload or "C5"
         env_id, a.variant, n_envs = bench.WORKLOADS[tag]
         over = dict(n_envs=n_envs, env_dynamics="synthetic")
+    for kv in a.override:
+        k, sep, v = kv.partition("=")
+        if not sep:
+            ap.error(f"--override takes K=V, got {kv!r}")
+        try:
+            over[k] = json.loads(v)
+        except ValueError:
+            over[k] = v
     if a.ab:
         a.rollouts = a.rollouts or 20
         if not a.n_envs:
