@@ -380,6 +380,46 @@ int launch_global_adv_sums(const int32_t *idx, int64_t n, int64_t B, const float
 int launch_global_adv_stats(const double *sums, int64_t n, int64_t Bg, float *stats, hipStream_t s);
 int launch_global_records(const double *sums, int64_t n, const LossArgs &la, float *metrics, hipStream_t s);
 int launch_sumsq_flat(const float *G, int64_t n, float *out, int nblocks, hipStream_t s);
+// raise a kernel's dynamic-LDS limit once (gs_mlp.hip; never inside a stream capture)
+int set_lds_limit(const void *fn, size_t bytes);
+
+// ---- one-hidden-layer actor-critic (gs_mlp1.hip): gs_mlp_dims.hidden2 == 0 ---------------------
+// Flat layout in the reference's state_dict order: backbone.0.weight[H][D], backbone.0.bias[H],
+// policy_head.weight[A][H], policy_head.bias[A], value_head.weight[1][H], value_head.bias[1].
+struct Layout1 {
+    int D, H, A;
+    int oW1, ob1, oWp, obp, oWv, obv, P;
+    __host__ __device__ static constexpr Layout1 make(int D, int H, int A)
+    {
+        Layout1 L{};
+        L.D = D; L.H = H; L.A = A;
+        L.oW1 = 0;
+        L.ob1 = L.oW1 + H * D;
+        L.oWp = L.ob1 + H;
+        L.obp = L.oWp + A * H;
+        L.oWv = L.obp + A;
+        L.obv = L.oWv + H;
+        L.P = L.obv + 1;
+        return L;
+    }
+    // head row a in [0, A]: a < A -> policy_head.weight[a], a == A -> value_head.weight
+    __host__ __device__ constexpr int head_row(int a) const { return a < A ? oWp + a * H : oWv; }
+    __host__ __device__ constexpr int head_bias(int a) const { return a < A ? obp + a : obv; }
+};
+// The entries of gs_ppo.hip dispatch here at their top when dims.hidden2 == 0.  mlp1_check_dims:
+// the supported envelope (include/gsamd.h, beside gs_mlp_dims) including the update kernel's LDS
+// rule.  mlp1_update: n_minibatches steps in ONE launch of one workgroup (loss_only: forward +
+// loss of one minibatch, gs_ppo_loss).
+int mlp1_check_dims(const gs_mlp_dims &d);
+size_t mlp1_update_lds_bytes(const gs_mlp_dims &d);
+int mlp1_policy_act(const float *params, const gs_mlp_dims &d, const float *obs, int64_t N, int mode, uint64_t rng_seed,
+                    uint64_t rng_counter, int64_t *actions, float *logp, float *value, float *obs_store,
+                    const uint64_t *clock, hipStream_t s);
+int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const gs_mlp_dims &d,
+                const gs_ppo_hparams &hp, const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n,
+                int64_t adam_step0, float *metrics, int32_t *stop_flag, bool loss_only, hipStream_t s);
+int mlp1_activation_stats(const float *params, const gs_mlp_dims &d, const gs_rollout_view &ro, const int32_t *idx,
+                          int64_t rows, double *part, hipStream_t s);
 
 // ---- bf16 MFMA operands of the NatureCNN path (GS_HP_BF16 performance mode) ----------------
 // 8 fp32 values -> one bf16 fragment of v_mfma_f32_16x16x32_bf16 / 32x32x16_bf16 (round to

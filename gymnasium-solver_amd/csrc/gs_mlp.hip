@@ -40,6 +40,7 @@
 #include <unordered_map>
 
 #include "gs_common.h"
+#include "gs_head.h"
 #include "gs_xgmi_dev.h"
 #include "gs_synth_env.h"
 #include "gs_cartpole_env.h"
@@ -94,14 +95,6 @@ __device__ __forceinline__ f32x4 mfma_bf16_pair(float4 a0, float4 a1, float4 b0,
 }
 __device__ __forceinline__ float4 f4(const float (&v)[4]) { return make_float4(v[0], v[1], v[2], v[3]); }
 
-// env-major sample index (utils/rollout_buffer.py:11-13) -> time-major buffer row
-__device__ __forceinline__ int sample_row(int s, int T, int N)
-{
-    const unsigned e = (unsigned)s / (unsigned)T;
-    const unsigned t = (unsigned)s - e * (unsigned)T;
-    return (int)(t * (unsigned)N + e);
-}
-
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v)
 {
@@ -112,39 +105,8 @@ __device__ __forceinline__ T wave_sum(T v)
 
 __host__ __device__ constexpr int round4(int n) { return (n + 3) & ~3; }
 
-constexpr int kNumSums = 14;   // metric sums of one minibatch (loss_row)
-
-// Sum NV per-thread values over the 256-thread block in a fixed order (deterministic),
-// through LDS (two levels of 16) — __shfl would lower to ds_bpermute chains (~100+ cycles
-// per step).  Every thread returns the totals.  scratch: NV*(256+16) elements of T.
-// In a block wider than 256 threads only threads 0..255 contribute (the others only meet the
-// barriers and read the totals), so the sum order is the 256-thread one.
-template <int NV, typename T>
-__device__ __forceinline__ void block_reduce(T (&v)[NV], T *scratch)
-{
-    const int tid = threadIdx.x;
-    if (tid < 256)
-#pragma unroll
-        for (int k = 0; k < NV; ++k) scratch[k * 256 + tid] = v[k];
-    __syncthreads();
-    T *part = scratch + NV * 256;
-    if (tid < NV * 16) {
-        const int k = tid >> 4, j = tid & 15;
-        T acc = 0;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) acc += scratch[k * 256 + j * 16 + m];
-        part[tid] = acc;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        T acc = 0;
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc += part[k * 16 + j];
-        v[k] = acc;
-    }
-    __syncthreads();
-}
+// kNumSums (the metric sums of one minibatch) and block_reduce (the fixed-order 256-thread sum):
+// gs_head.h
 
 __device__ __forceinline__ void store_component_norms(double (&hq)[2], double total_sq, float gscale, float *rec,
                                                       double *scratch)
@@ -204,17 +166,6 @@ __device__ __forceinline__ void copy_to_lds(float *dst, const float *src, int n)
     }
 }
 
-// clip_grad_norm_'s coefficient (max_norm <= 0: no clip; agents/base_agent.py:591-621)
-__device__ __forceinline__ float clip_coef(float total, const AdamArgs &aa)
-{
-    float coef = 1.0f;
-    if (aa.max_norm > 0.0f) {
-        coef = aa.max_norm / (total + 1e-6f);
-        coef = fminf(coef, 1.0f);
-    }
-    return coef;
-}
-
 // Per-component pre-clip gradient norms of one step (utils/models.py:196-230 compute_grad_norms,
 // recorded at agents/base_agent.py:607-608): policy_head and value_head from their gradients in G,
 // backbone as the rest of the step's squared total (every component of the MLP policy is one of
@@ -236,24 +187,7 @@ __host__ __device__ inline int64_t head_grad_offset(const Layout &L, int u, bool
     return L.head_bias(u - nw);
 }
 
-// One parameter of torch.optim.Adam (single-tensor path, amsgrad off) on the clipped gradient;
-// shared by k_clip_adam and the lagged step in k_fwd_hidden so both round identically.
-// inv_bc2s = f32(1 / sqrt(1 - beta2^t)) (host, double), so the bias correction is a multiply.
-__device__ __forceinline__ float adam_param(float graw, float coef, float &m, float &v, float &p,
-                                            const AdamArgs &aa, float neg_step, float inv_bc2s)
-{
-    const float g = graw * coef;
-    m = m + aa.one_minus_b1 * (g - m);            // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * aa.b2;                                // exp_avg_sq.mul_(beta2)
-    v = v + (aa.one_minus_b2 * g) * g;            //   .addcmul_(grad, grad, 1 - beta2)
-    // hardware sqrt and reciprocal (v_sqrt_f32, v_rcp_f32: ~1 ulp each) instead of torch's
-    // correctly rounded divisions: IEEE division lowers to a v_div_scale / v_div_fmas /
-    // v_div_fixup sequence serialised through VCC, ~10x the latency, and this runs 4-21 times
-    // per thread on the minibatch chain's critical path
-    const float denom = __builtin_amdgcn_sqrtf(v) * inv_bc2s + aa.eps;
-    p = p + neg_step * (m * __builtin_amdgcn_rcpf(denom));
-    return g;
-}
+// clip_coef (clip_grad_norm_'s coefficient) and adam_param (one parameter's Adam step): gs_head.h
 
 // ------------------------------------------------------------------------------------
 // k_fwd_hidden: grid (ceil(H2/16), ceil(rows/16)), 256 threads.
@@ -1049,7 +983,6 @@ __global__ __launch_bounds__(ADAM ? kFwdAdamThreads : 256) void k_fwd_chain(
                                                 t.zpart, nullptr, nullptr, RowGather{}, ff, t.h2mask, af);
 }
 
-static int set_lds_limit(const void *fn, size_t bytes);
 template <class F>
 static int with_shape(const Layout &L, int64_t B, F &&f);
 
@@ -1073,41 +1006,8 @@ int launch_fwd_hidden(const float *params, const Layout &L, const float *obs, co
     });
 }
 
-// ------------------------------------------------------------------------------------
-// per-row categorical head math shared by rollout and loss kernels
-// ------------------------------------------------------------------------------------
-struct HeadRow {
-    float lse;    // logsumexp of raw logits
-    float m2;     // max of normalised logits
-    float S;      // sum exp(ln - m2)
-};
-
-// z: raw logits of one row held in registers (AMAX = compile-time bound on A).
-template <int AMAX>
-__device__ __forceinline__ HeadRow head_stats(const float (&z)[AMAX + 1], int A)
-{
-    float m = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-        if (a < A) m = fmaxf(m, z[a]);
-    float se = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-        if (a < A) se += expf(z[a] - m);
-    HeadRow h;
-    h.lse = m + logf(se);
-    float m2 = -INFINITY;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-        if (a < A) m2 = fmaxf(m2, z[a] - h.lse);
-    h.m2 = m2;
-    float S = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-        if (a < A) S += expf((z[a] - h.lse) - m2);
-    h.S = S;
-    return h;
-}
+// the per-row categorical head math shared by the rollout and loss kernels (HeadRow, head_stats,
+// head_act_row, mix64) and the loss row (loss_row, write_metrics): gs_head.h
 
 // logits/value of row r from the per-16-column partials (+ bias): the row's partials are
 // contiguous ([row][col-block][A+1]) and are loaded as one burst before any add.
@@ -1166,67 +1066,10 @@ __device__ __forceinline__ void gather_head_row(const float *__restrict__ zpart,
         if (a < A1) z[a] += P[L.head_bias(a)];
 }
 
-__device__ __forceinline__ uint64_t mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // ------------------------------------------------------------------------------------
-// k_heads_act: rollout head — logits/value from partials, action select, log_prob.
-// one thread per env row.
+// k_heads_act: rollout head — logits/value from partials, action select, log_prob
+// (head_act_row, gs_head.h).  one thread per env row.
 // ------------------------------------------------------------------------------------
-// value, action (sampled / argmax / replayed) and its log-prob of one env row from its raw
-// logits | value z; ctr = the rollout step's counter of the counter-based uniform
-template <int AMAX>
-__device__ __forceinline__ void head_act_row(const float (&z)[AMAX + 1], int A, int mode, uint64_t seed, uint64_t ctr,
-                                             int64_t r, int64_t *__restrict__ action, float *__restrict__ logp,
-                                             float *__restrict__ value)
-{
-    float v = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX + 1; ++a)
-        if (a == A) v = z[a];
-    if (value) *value = v;
-    if (!action) return;
-    const HeadRow h = head_stats<AMAX>(z, A);
-    int act = 0;
-    if (mode == 2) {            // replay recorded actions
-        act = (int)*action;
-    } else if (mode == 1) {     // Categorical.mode = probs.argmax(-1), first max wins
-        float best = -INFINITY;
-#pragma unroll
-        for (int a = 0; a < AMAX; ++a) {
-            if (a < A) {
-                const float p = expf((z[a] - h.lse) - h.m2) / h.S;
-                if (p > best) { best = p; act = a; }
-            }
-        }
-        *action = act;
-    } else {                    // inverse-CDF sample with a counter-based uniform
-        const uint64_t hh = mix64(mix64(mix64(seed) ^ ctr) ^ (uint64_t)r);
-        const float u = (float)(hh >> 40) * (1.0f / 16777216.0f);
-        float c = 0.0f;
-        act = -1;
-#pragma unroll
-        for (int a = 0; a < AMAX; ++a) {
-            if (a < A) {
-                c += expf((z[a] - h.lse) - h.m2) / h.S;
-                if (act < 0 && u < c) act = a;
-            }
-        }
-        if (act < 0) act = A - 1;
-        *action = act;
-    }
-    float za = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a)
-        if (a == act) za = z[a];
-    *logp = za - h.lse;
-}
-
 template <class S>
 __global__ __launch_bounds__(256) void k_heads_act(const float *__restrict__ P, Layout Lrt,
                                                    const float *__restrict__ zpart, int64_t rows, int mode,
@@ -1607,120 +1450,6 @@ int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T
     GS_REQUIRE(rollout_env_fits(L, GS_ENV_MOUNTAINCAR),
                "gs_rollout_mountaincar: the policy is not MountainCar's (obs dim 2, 3 actions) or does not fit in LDS");
     return launch_rollout_sh<ShapeR<4>, RolloutMountainCarEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
-}
-
-// ------------------------------------------------------------------------------------
-// One minibatch row of PPOAgent.losses_for_batch (agents/ppo/ppo_agent.py:21-152) with its
-// analytic gradients: z = raw logits | value, adv already batch-normalised.  Writes
-// dLoss/dlogits | dLoss/dvalue to dzr and adds the row's terms to the 14 metric sums.
-// ------------------------------------------------------------------------------------
-template <int AMAX>
-__device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int act, float olp, float ov, float adv,
-                                         float ret, const LossArgs &la, float invB, float *__restrict__ dzr,
-                                         double (&acc)[kNumSums])
-{
-    float v = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX + 1; ++a)
-        if (a == A) v = z[a];
-    const HeadRow h = head_stats<AMAX>(z, A);
-    const float invS = 1.0f / h.S;
-    // ln = normalised logits, p = softmax(ln) (Categorical.probs), pe = exp(ln)
-    float ln[AMAX], p[AMAX];
-    float H = 0.0f, lp = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a) {
-        ln[a] = z[a] - h.lse;
-        p[a] = a < A ? expf(ln[a] - h.m2) * invS : 0.0f;
-        if (a < A) {
-            H += fmaxf(ln[a], -FLT_MAX) * p[a];   // entropy: -sum clamp(ln, f32min) * p
-            if (a == act) lp = ln[a];
-        }
-    }
-    H = -H;
-    const float ratio = expf(lp - olp);
-    const float rc = fminf(fmaxf(ratio, la.clip_lo), la.clip_hi);
-    const float s1 = adv * ratio, s2 = adv * rc;
-    const float mn = fminf(s1, s2);
-    const float vdelta = v - ov;
-    const float du = v - ret;
-    const float vu = du * du;
-    const float vcl = ov + fminf(fmaxf(vdelta, -la.clip_vf), la.clip_vf);
-    const float dc = vcl - ret;
-    const float vc = dc * dc;
-    const float vmax = fmaxf(vu, vc);
-    const float ldiff = fminf(fmaxf(lp - olp, -20.0f), 20.0f);
-    const float r2 = expf(ldiff);
-    const float akl = (r2 - 1.0f) - logf(r2);
-    const float rv = ret - v;
-    acc[0] += (double)mn;
-    acc[1] += (double)vmax;
-    acc[2] += (double)H;
-    acc[3] += (ratio < la.clip_lo || ratio > la.clip_hi) ? 1.0 : 0.0;
-    acc[4] += (vdelta < -la.clip_vf || vdelta > la.clip_vf) ? 1.0 : 0.0;
-    acc[5] += (double)(olp - lp);
-    acc[6] += (double)akl;
-    acc[7] += (double)rv;
-    acc[8] += (double)rv * (double)rv;
-    acc[9] += (double)ret;
-    acc[10] += (double)ret * (double)ret;
-    acc[11] += (double)adv;
-    acc[12] += (double)adv * (double)adv;
-    // ---- analytic gradients (torch autograd tie rules: min/max ties split halves)
-    const float ga = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float gb = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float inclip = (ratio >= la.clip_lo && ratio <= la.clip_hi) ? 1.0f : 0.0f;
-    const float g_mn = -invB;
-    const float dratio = adv * (g_mn * ga) + adv * (g_mn * gb) * inclip;
-    const float dlp = dratio * ratio;
-    const float dH = -la.ent_coef * invB;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a) {
-        if (a < A) {
-            const float pe = expf(ln[a]);   // softmax(z) as seen by logsumexp backward
-            float g = dlp * ((a == act ? 1.0f : 0.0f) - pe);
-            g += dH * (-p[a] * (ln[a] + H));
-            dzr[a] = g;
-        }
-    }
-    const float hu = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float hc = vc > vu ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float invc = (vdelta >= -la.clip_vf && vdelta <= la.clip_vf) ? 1.0f : 0.0f;
-    const float gv = la.vf_coef * invB;
-    dzr[A] = (gv * hu) * (2.0f * du) + (gv * hc) * (2.0f * dc) * invc;
-}
-
-// metrics record from the 14 sums (shared by k_loss and the fused path's k_metrics_all)
-__device__ __forceinline__ void write_metrics(const double *t, double Bd, const LossArgs &la, float *metrics,
-                                              bool adv_stats)
-{
-    const float pl = (float)(-t[0] / Bd);
-    const float vl = (float)(t[1] / Bd);
-    const float ent = (float)(t[2] / Bd);
-    const float loss = pl + la.vf_coef * vl + la.ent_coef * (-ent);
-    const double var_rv = (t[8] - t[7] * t[7] / Bd) / (Bd - 1.0);
-    const double var_r = (t[10] - t[9] * t[9] / Bd) / (Bd - 1.0);
-    const float approx_kl = (float)(t[6] / Bd);
-    const bool kl_stop = la.target_kl > 0.0f && approx_kl > la.target_kl;
-    metrics[GS_M_LOSS] = loss;
-    metrics[GS_M_POLICY_LOSS] = pl;
-    metrics[GS_M_VALUE_LOSS] = vl;
-    metrics[GS_M_ENTROPY] = ent;
-    metrics[GS_M_CLIP_FRAC] = (float)(t[3] / Bd);
-    metrics[GS_M_CLIP_FRAC_VF] = (float)(t[4] / Bd);
-    metrics[GS_M_EXPLAINED_VAR] = (float)(1.0 - var_rv / var_r);
-    metrics[GS_M_KL] = (float)(t[5] / Bd);
-    metrics[GS_M_APPROX_KL] = approx_kl;
-    if (adv_stats) {
-        const double amean = t[11] / Bd;
-        const double astd = sqrt(fmax(0.0, (t[12] - t[11] * t[11] / Bd) / (Bd - 1.0)));
-        metrics[GS_M_ADV_NORM_MEAN] = la.normalize ? (float)amean : 0.0f;
-        metrics[GS_M_ADV_NORM_STD] = la.normalize ? (float)astd : 0.0f;
-    }
-    metrics[GS_M_KL_STOP] = kl_stop ? 1.0f : 0.0f;
-    metrics[GS_M_SKIPPED] = kl_stop ? 1.0f : 0.0f;
-    metrics[GS_M_UNEVALUATED] = 0.0f;
-    metrics[GS_M_RES1] = 0.0f;
 }
 
 // ------------------------------------------------------------------------------------
@@ -3142,7 +2871,7 @@ int rows_b(const Layout &L, int64_t B)
 
 // Raise a kernel's dynamic-LDS limit once (never inside a stream capture: the first
 // eager launch or prepare_kernels() does it before any graph is recorded).
-static int set_lds_limit(const void *fn, size_t bytes)
+int set_lds_limit(const void *fn, size_t bytes)
 {
     static std::mutex mu;
     static std::unordered_map<const void *, size_t> done;

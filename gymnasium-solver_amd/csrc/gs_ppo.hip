@@ -87,10 +87,21 @@ static RowGather gather_of(const gs_rollout_view &ro, const Workspace &ws)
 
 using namespace gs;
 
-extern "C" int64_t gs_mlp_param_count(gs_mlp_dims dims) { return layout_of(dims).P; }
+// gs_mlp_dims.hidden2 == 0: one hidden layer (gs_mlp1.hip).  The entries that serve it dispatch
+// at their top; the others refuse it by name.
+static bool one_layer(const gs_mlp_dims &d) { return d.hidden2 == 0; }
+#define GS_REFUSE_ONE_LAYER(dims, what) \
+    GS_REQUIRE(!one_layer(dims), what ": not available for a policy with one hidden layer (hidden2 == 0)")
+
+extern "C" int64_t gs_mlp_param_count(gs_mlp_dims dims)
+{
+    if (one_layer(dims)) return Layout1::make(dims.obs_dim, dims.hidden1, dims.n_actions).P;
+    return layout_of(dims).P;
+}
 
 extern "C" size_t gs_policy_scratch_bytes(gs_mlp_dims dims, int64_t N)
 {
+    if (one_layer(dims)) return 256;     // the one-hidden-layer forward needs no scratch
     const Layout L = layout_of(dims);
     return align256((size_t)n_col_blocks(L.H2) * N * (L.A + 1) * sizeof(float));
 }
@@ -99,6 +110,11 @@ extern "C" int gs_policy_act(const float *params, gs_mlp_dims dims, const float 
                              uint64_t rng_seed, uint64_t rng_counter, int64_t *actions, float *logp, float *value,
                              float *obs_store, void *scratch, const uint64_t *clock, void *stream)
 {
+    if (one_layer(dims)) {
+        GS_REQUIRE(actions && logp && value, "gs_policy_act: null buffer");
+        return mlp1_policy_act(params, dims, obs, N, mode, rng_seed, rng_counter, actions, logp, value, obs_store,
+                               clock, (hipStream_t)stream);
+    }
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(N > 0, "gs_policy_act: N must be > 0");
@@ -117,6 +133,10 @@ extern "C" int gs_policy_act(const float *params, gs_mlp_dims dims, const float 
 extern "C" int gs_rollout_synth_supported(gs_mlp_dims dims, int *supported)
 {
     GS_REQUIRE(supported, "gs_rollout_synth_supported: null output");
+    if (one_layer(dims)) {      // no one-launch rollout for one hidden layer: the step graph
+        *supported = 0;
+        return mlp1_check_dims(dims);
+    }
     int rc = check_dims(dims);
     if (rc) return rc;
     *supported = rollout_synth_fits(layout_of(dims)) ? 1 : 0;
@@ -131,6 +151,7 @@ extern "C" int gs_rollout_synth(const float *params, gs_mlp_dims dims, int64_t N
                                 float *logp_rows, float *value_rows, float *reward_rows, uint8_t *done_rows,
                                 uint8_t *timeout_rows, void *stream)
 {
+    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_synth");
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_synth: bad N / T");
@@ -150,6 +171,10 @@ extern "C" int gs_rollout_synth(const float *params, gs_mlp_dims dims, int64_t N
 extern "C" int gs_rollout_env_supported(gs_mlp_dims dims, int kind, int *supported)
 {
     GS_REQUIRE(supported, "gs_rollout_env_supported: null output");
+    if (one_layer(dims)) {
+        *supported = 0;
+        return mlp1_check_dims(dims);
+    }
     int rc = check_dims(dims);
     if (rc) return rc;
     const Layout L = layout_of(dims);
@@ -164,6 +189,7 @@ extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, 
                               float *obs_rows, int64_t *action_rows, float *logp_rows, float *value_rows,
                               float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows, void *stream)
 {
+    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_env");
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_env: bad N / T");
@@ -193,6 +219,7 @@ extern "C" int gs_rollout_mountaincar(const float *params, gs_mlp_dims dims, int
                                       float *value_rows, float *reward_rows, uint8_t *done_rows,
                                       uint8_t *timeout_rows, void *stream)
 {
+    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_mountaincar");
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_mountaincar: bad N / T");
@@ -215,6 +242,9 @@ extern "C" int gs_rollout_mountaincar(const float *params, gs_mlp_dims dims, int
 extern "C" int gs_policy_value(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, float *value,
                                void *scratch, void *stream)
 {
+    if (one_layer(dims))
+        return mlp1_policy_act(params, dims, obs, N, 0, 0, 0, nullptr, nullptr, value, nullptr, nullptr,
+                               (hipStream_t)stream);
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(N > 0 && params && obs && value && scratch, "gs_policy_value: bad argument");
@@ -230,6 +260,7 @@ extern "C" int gs_policy_value(const float *params, gs_mlp_dims dims, const floa
 
 extern "C" size_t gs_ppo_workspace_bytes(gs_mlp_dims dims, int64_t batch)
 {
+    if (one_layer(dims)) return mlp1_check_dims(dims) ? 0 : 256;    // the update's state lives in LDS
     return carve_workspace(nullptr, layout_of(dims), batch).bytes;
 }
 
@@ -286,6 +317,7 @@ FusedWs carve_fused(void *base, const Layout &L, int64_t B, int64_t n)
 
 extern "C" size_t gs_ppo_update_workspace_bytes(gs_mlp_dims dims, int64_t batch, int64_t n_minibatches)
 {
+    if (one_layer(dims)) return mlp1_check_dims(dims) || batch < 1 || n_minibatches < 0 ? 0 : 256;
     if (check_dims(dims) || batch < 1 || n_minibatches < 0) return 0;
     const Layout L = layout_of(dims);
     if (!has_fused(L, batch)) return carve_workspace(nullptr, L, batch).bytes;
@@ -490,6 +522,12 @@ extern "C" int gs_ppo_minibatch_step(float *params, float *grads, float *adam_m,
                                      int64_t adam_step, float *metrics, int32_t *stop_flag, void *workspace,
                                      gs_comm *comm, void *stream)
 {
+    if (one_layer(dims)) {      // the one-launch update with n = 1
+        GS_REQUIRE(!comm, "gs_ppo_minibatch_step: no gradient exchange for a policy with one hidden layer");
+        GS_REQUIRE(adam_step >= 1, "adam_step is 1-based");
+        return mlp1_update(params, grads, adam_m, adam_v, dims, hp, ro, idx, batch, 1, adam_step - 1, metrics,
+                           stop_flag, false, (hipStream_t)stream);
+    }
     int rc = validate_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(adam_step >= 1, "adam_step is 1-based");
@@ -506,6 +544,7 @@ extern "C" int gs_ppo_minibatch_step(float *params, float *grads, float *adam_m,
 extern "C" int gs_mlp_activation_stats(const float *params, gs_mlp_dims dims, gs_rollout_view ro, const int32_t *idx,
                                        int64_t rows, double *part, void *stream)
 {
+    if (one_layer(dims)) return mlp1_activation_stats(params, dims, ro, idx, rows, part, (hipStream_t)stream);
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(params && ro.obs && part && rows >= 1, "gs_mlp_activation_stats: null buffer or no rows");
@@ -516,6 +555,9 @@ extern "C" int gs_mlp_activation_stats(const float *params, gs_mlp_dims dims, gs
 extern "C" int gs_ppo_loss(const float *params, gs_mlp_dims dims, gs_ppo_hparams hp, gs_rollout_view ro,
                            const int32_t *idx, int64_t batch, float *metrics, void *workspace, void *stream)
 {
+    if (one_layer(dims))    // steps 1-3 of the one-launch update on one minibatch; nothing is written but the record
+        return mlp1_update(const_cast<float *>(params), nullptr, nullptr, nullptr, dims, hp, ro, idx, batch, 1, 0,
+                           metrics, nullptr, true, (hipStream_t)stream);
     int rc = validate_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(params && idx && metrics, "gs_ppo_loss: null buffer");
@@ -536,6 +578,7 @@ extern "C" int gs_ppo_stage(int stage, float *params, float *grads, float *adam_
                             gs_ppo_hparams hp, gs_rollout_view ro, const int32_t *idx, int64_t batch,
                             int64_t adam_step, float *metrics, void *workspace, void *stream)
 {
+    GS_REFUSE_ONE_LAYER(dims, "gs_ppo_stage");
     int rc = validate_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(stage >= 0 && stage <= 7, "gs_ppo_stage: stage %d not in [0, 7]", stage);
@@ -646,6 +689,11 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
                       void *workspace, size_t workspace_bytes, gs_comm *comm, int use_graph, void *stream,
                       const gs_ppo_global *glob)
 {
+    if (one_layer(dims)) {      // one launch of one workgroup for all the steps (use_graph: nothing to capture)
+        GS_REQUIRE(!comm, "gs_ppo_update: no gradient exchange for a policy with one hidden layer");
+        return mlp1_update(params, grads, adam_m, adam_v, dims, hp, ro, idx, batch, n_minibatches, adam_step0, metrics,
+                           stop_flag, false, (hipStream_t)stream);
+    }
     int rc = validate_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(n_minibatches >= 0 && adam_step0 >= 0, "bad n_minibatches/adam_step0");
@@ -906,6 +954,7 @@ extern "C" int gs_ppo_update_global(float *params, float *grads, float *adam_m, 
                                     void *workspace, size_t workspace_bytes, gs_comm *comm, int use_graph,
                                     const gs_ppo_global *glob, void *stream)
 {
+    GS_REFUSE_ONE_LAYER(dims, "gs_ppo_update_global");
     GS_REQUIRE(glob && glob->batch_global >= 2 && glob->metric_sums, "gs_ppo_update_global: bad global arguments");
     GS_REQUIRE(!hp.normalize_adv || glob->adv_stats, "gs_ppo_update_global: normalize_adv needs adv_stats");
     GS_REQUIRE(glob->batch_global >= batch || !comm, "gs_ppo_update_global: batch_global < local rows");
@@ -952,6 +1001,7 @@ extern "C" int gs_ppo_graph_cache_info(int64_t *n_entries, int64_t *n_captures)
 extern "C" int gs_ppo_exchange_inside_bwd(gs_comm *comm, gs_mlp_dims dims, int64_t batch, int *inside)
 {
     GS_REQUIRE(comm && inside, "gs_ppo_exchange_inside_bwd: null argument");
+    GS_REFUSE_ONE_LAYER(dims, "gs_ppo_exchange_inside_bwd");
     int rc = check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(batch >= 2 && batch <= 1024, "batch %lld outside [2, 1024]", (long long)batch);

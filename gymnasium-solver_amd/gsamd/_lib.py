@@ -48,6 +48,15 @@ class MountainCarWrappers(ctypes.Structure):
                 ("bonus_type", ctypes.c_int32), ("min_count", ctypes.c_int32), ("bonus_scale", ctypes.c_double)]
 
 
+GS_ENCODINGS = {"array": 0, "binary": 1, "onehot": 2}          # GS_ENC_*
+
+
+class TabularSpec(ctypes.Structure):
+    """gs_tabular_spec (include/gsamd.h): the shape of a tabular env and its observation encoding."""
+    _fields_ = [("n_states", ctypes.c_int32), ("n_actions", ctypes.c_int32), ("n_outcomes", ctypes.c_int32),
+                ("n_starts", ctypes.c_int32), ("encoding", ctypes.c_int32), ("obs_dim", ctypes.c_int32)]
+
+
 class PPOHparams(ctypes.Structure):
     _fields_ = [("clip_range", ctypes.c_float), ("clip_range_vf", ctypes.c_float), ("vf_coef", ctypes.c_float),
                 ("ent_coef", ctypes.c_float), ("max_grad_norm", ctypes.c_float), ("lr", ctypes.c_float),
@@ -153,6 +162,9 @@ def _load():
         "gs_rollout_mountaincar": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
                                                   MountainCarWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                                   vp, vp, vp]),
+        "gs_tabular_reset": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, i64, u64, i64, vp]),
+        "gs_tabular_step": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp,
+                                           vp, vp, vp, vp, vp]),
         "gs_atari_preprocess": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),
         "gs_atari_render": (ctypes.c_int, [vp, i64, u64, i64, u64, vp]),
         "gs_atari_env_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, u64, i64, vp]),
@@ -196,7 +208,7 @@ EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_norma
             "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
             "gs_cnn_ppo_update_global",
             "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",
-            "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
+            "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar", "gs_tabular_reset", "gs_tabular_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
             "gs_comm_init", "gs_comm_xgmi_create", "gs_comm_xgmi_connect", "gs_comm_status", "gs_comm_error_record",
             "gs_comm_xgmi_set_colocation", "gs_comm_xgmi_set_bwd_exchange", "gs_comm_xgmi_reset",
             "gs_comm_allreduce_mean_f32", "gs_comm_allreduce_sum_f64", "gs_ppo_global_adv_stats",

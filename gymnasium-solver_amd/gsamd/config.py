@@ -75,6 +75,8 @@ class PPOConfig:
     #   "cartpole"  device CartPole-v1 dynamics
     #   "acrobot"   device Acrobot-v1 dynamics
     #   "mountaincar" device MountainCar-v0 dynamics with the config's env_wrappers
+    #   "frozenlake" / "taxi" the device tabular env on gsamd.toytext's tables, with the config's
+    #               DiscreteEncoder and (FrozenLake) map kwargs
     env_dynamics: str = "auto"
     # data-parallel semantics of a multi-rank update:
     #   "local"  every rank takes B-row minibatches of its own samples (weak scaling, global batch G·B)
@@ -170,6 +172,14 @@ class PPOConfig:
         obs = (self.spec or {}).get("observation_space", {})
         variants = obs.get("variants", {})
         default = variants.get(obs.get("default", "state"), {})
+        if not default.get("shape") and default.get("n"):
+            # a Discrete space (`n` states): the observation is what the config's DiscreteEncoder makes of it
+            tab = resolve_tabular_env(self)
+            if tab is not None:
+                return int(tab["obs_dim"])
+            enc = [w for w in (self.env_wrappers or []) if isinstance(w, dict) and w.get("id") == "DiscreteEncoder"]
+            if enc and enc[-1].get("encoding", "binary") in DISCRETE_ENCODINGS:
+                return discrete_encoding_dim(enc[-1].get("encoding", "binary"), int(default["n"]))
         shape = default.get("shape") or [4]
         return int(shape[0])
 
@@ -183,10 +193,68 @@ class PPOConfig:
 _FIELDS = {f.name for f in dataclasses.fields(PPOConfig)}
 _ALIASES = {"LunarLander-v2": "LunarLander-v3"}
 
-ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot", "mountaincar")
+ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi")
 # env ids whose dynamics the device implements, as BaseAgent.build_env would build them from a
-# config without wrappers / env kwargs / observation normalisation
-DEVICE_DYNAMICS = {"CartPole-v1": "cartpole", "Acrobot-v1": "acrobot", "MountainCar-v0": "mountaincar"}
+# config without wrappers / env kwargs / observation normalisation; the two
+# tabular envs need exactly the DiscreteEncoder wrapper (resolve_tabular_env)
+DEVICE_DYNAMICS = {"CartPole-v1": "cartpole", "Acrobot-v1": "acrobot", "MountainCar-v0": "mountaincar",
+                   "FrozenLake-v1": "frozenlake", "Taxi-v3": "taxi"}
+TABULAR_KINDS = ("frozenlake", "taxi")
+DISCRETE_ENCODINGS = ("array", "binary", "onehot")      # gym_wrappers/discrete_encoder.py
+MAX_POLICY_OBS_DIM = 64                                 # csrc/gs_common.h kMaxObsDim
+FROZENLAKE_MAPS = {"4x4": 16, "8x8": 64}                # map_name -> states
+TAXI_STATES = 500
+
+
+def discrete_encoding_dim(encoding: str, n_states: int) -> int:
+    """Observation length of the reference's DiscreteEncoder (gym_wrappers/discrete_encoder.py:26-50)."""
+    if encoding == "array":
+        return 1
+    if encoding == "binary":
+        return max(1, (int(n_states) - 1).bit_length())     # max(1, ceil(log2 n)) in integers
+    if encoding == "onehot":
+        return int(n_states)
+    raise ValueError(f"encoding must be one of {DISCRETE_ENCODINGS}, got {encoding!r}")
+
+
+def resolve_tabular_env(cfg) -> Optional[Dict[str, Any]]:
+    """What the device tabular env needs from a FrozenLake-v1 / Taxi-v3 config, or None when the
+    device does not build that env (the host env then): env_wrappers exactly one
+    {"id": "DiscreteEncoder"[, "encoding": array | binary | onehot]} (a missing encoding is the
+    class default, binary); for FrozenLake env_kwargs with only is_slippery (bool) and map_name
+    ("4x4" | "8x8"), for Taxi none; a onehot of more than 64 states exceeds the policy's obs_dim.
+    An unwrapped Discrete env has no float observation, so a config without the encoder is host
+    too.  Returns {kind, encoding, n_states, obs_dim, map_name, is_slippery}."""
+    kind = DEVICE_DYNAMICS.get(str(getattr(cfg, "env_id", "")))
+    if kind not in TABULAR_KINDS:
+        return None
+    wrappers = getattr(cfg, "env_wrappers", None) or []
+    if len(wrappers) != 1 or not isinstance(wrappers[0], dict):
+        return None
+    w = wrappers[0]
+    if w.get("id") != "DiscreteEncoder" or set(w) - {"id", "encoding"}:
+        return None
+    encoding = w.get("encoding", "binary")
+    if encoding not in DISCRETE_ENCODINGS:
+        return None
+    kwargs = getattr(cfg, "env_kwargs", None) or {}
+    map_name, slippery = "4x4", True            # gymnasium's FrozenLake-v1 defaults
+    if kind == "frozenlake":
+        if set(kwargs) - {"is_slippery", "map_name"}:
+            return None
+        map_name, slippery = kwargs.get("map_name", map_name), kwargs.get("is_slippery", slippery)
+        if map_name not in FROZENLAKE_MAPS or not isinstance(slippery, bool):
+            return None
+        n_states = FROZENLAKE_MAPS[map_name]
+    else:
+        if kwargs:
+            return None
+        n_states = TAXI_STATES
+    obs_dim = discrete_encoding_dim(encoding, n_states)
+    if obs_dim > MAX_POLICY_OBS_DIM:
+        return None
+    return dict(kind=kind, encoding=encoding, n_states=n_states, obs_dim=obs_dim, map_name=map_name,
+                is_slippery=slippery)
 
 # The env_wrappers the device MountainCar-v0 applies itself (csrc/gs_mountaincar_env.h), with the
 # keyword arguments and defaults of the reference's classes
@@ -248,11 +316,12 @@ def resolve_mountaincar_wrappers(wrappers) -> Optional[List[Tuple[str, Dict[str,
 
 def device_env_kind(cfg) -> Optional[str]:
     """The device env a config trains on when the caller passes no env: "synthetic",
-    "cartpole", "acrobot", "mountaincar", or None when the config names an env the device does not
-    simulate — the caller then passes the host VectorEnv the reference would build
+    "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi", or None when the config names an env
+    the device does not simulate — the caller then passes the host VectorEnv the reference would build
     (agents/base_agent.py:129-192 → utils/environment.py:421-425 build_env_from_config).
     MountainCar-v0 may carry the env_wrappers the device applies itself
-    (resolve_mountaincar_wrappers); any wrapper on another env means the host env."""
+    (resolve_mountaincar_wrappers), FrozenLake-v1 / Taxi-v3 carry exactly the DiscreteEncoder
+    (resolve_tabular_env); any wrapper on another env means the host env."""
     mode = str(getattr(cfg, "env_dynamics", None) or "auto")
     if mode != "auto":
         return mode
@@ -260,6 +329,10 @@ def device_env_kind(cfg) -> Optional[str]:
         return None
     kind = DEVICE_DYNAMICS.get(str(getattr(cfg, "env_id", "")))
     wrappers = getattr(cfg, "env_wrappers", None)
+    if kind in TABULAR_KINDS:       # FrozenLake-v1 / Taxi-v3: the DiscreteEncoder and the map kwargs are the env's own
+        ok = (resolve_tabular_env(cfg) is not None and not getattr(cfg, "normalize_obs", False)
+              and getattr(cfg, "frame_stack", None) in (None, 0, 1))
+        return kind if ok else None
     if kind == "mountaincar":
         unwrapped = resolve_mountaincar_wrappers(wrappers) is not None
     else:

@@ -65,15 +65,21 @@ def reference_init(obs_dim: int, hidden: Sequence[int], n_actions: int) -> "Orde
 
 
 class DeviceMLPActorCritic:
-    """Two-hidden-layer ReLU actor-critic whose forward runs in libgsamd kernels."""
+    """ReLU actor-critic with one or two hidden layers whose forward runs in libgsamd kernels
+    (one layer, the reference's mlp_tiny: MlpDims.hidden2 == 0, csrc/gs_mlp1.hip)."""
 
     def __init__(self, obs_dim: int, hidden_dims: Tuple[int, ...], n_actions: int, device="cuda",
                  init: bool = True):
-        if len(hidden_dims) != 2:
-            raise ValueError(f"device MLP path implements two hidden layers, got {hidden_dims}")
+        if len(hidden_dims) not in (1, 2):
+            raise ValueError(f"device MLP path implements one or two hidden layers, got {hidden_dims}")
         self.obs_dim, self.hidden_dims, self.n_actions = int(obs_dim), tuple(int(h) for h in hidden_dims), int(n_actions)
-        self.dims = MlpDims(self.obs_dim, self.hidden_dims[0], self.hidden_dims[1], self.n_actions)
+        if any(h <= 0 for h in self.hidden_dims):
+            raise ValueError(f"hidden layer widths must be positive, got {hidden_dims}")
+        self.dims = MlpDims(self.obs_dim, self.hidden_dims[0], self.hidden_dims[1] if len(self.hidden_dims) == 2 else 0,
+                            self.n_actions)
         self.n_params = int(lib.gs_mlp_param_count(self.dims))
+        if self.n_params != sum(int(torch.Size(s).numel()) for _, s in self.shapes()):
+            raise ValueError(f"libgsamd counts {self.n_params} parameters for {self.hidden_dims}")
         self.device = torch.device(device)
         self.params = torch.zeros(self.n_params, dtype=torch.float32, device=self.device)
         self._scratch = {}

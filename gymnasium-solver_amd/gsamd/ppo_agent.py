@@ -26,11 +26,11 @@ import ctypes
 
 from ._lib import ACT_SLOT, GS_HP_ACT_STATS, GS_HP_BF16, GS_NUM_METRICS, M, PPOGlobal, PPOHparams, RolloutView, RolloutViewU8, check, lib, ptr, stream_handle
 from .atari_env import DeviceAtariVecEnv
-from .config import device_env_kind
+from .config import TABULAR_KINDS, device_env_kind, resolve_tabular_env
 from .cnn import DeviceCNNActorCritic
 from .policy import DeviceMLPActorCritic
 from .rollout import (DeviceAcrobotVecEnv, DeviceCartPoleVecEnv, DeviceMountainCarVecEnv, DeviceRolloutCollector,
-                      DeviceSyntheticVecEnv)
+                      DeviceSyntheticVecEnv, DeviceTabularVecEnv)
 from .samplers import IndexStreamPrefetcher, MultiPassRandomSampler, index_stream, rank_share
 from .distributed import allreduce_sum_f64, broadcast_int, check_replicas, comm_status, world_active
 from . import distributed as _dist
@@ -81,12 +81,26 @@ class DevicePPOAgent:
         self._staged = None                          # a tensor batch's T=1 rollout view (losses_for_batch)
         # optional per-epoch (start, update-start, end) events on the launch stream (bench.py)
         self.phase_events = None
+        self._check_one_layer_policy()
         self.build_env("train", env)
         self.build_models()
         self.build_rollout_collector("train")
         self.configure_optimizers()
 
     # ---- construction (base_agent.py:103-222) -------------------------------------------
+    def _check_one_layer_policy(self) -> None:
+        """A policy with one hidden layer (mlp_tiny) updates in one launch of one workgroup
+        (csrc/gs_mlp1.hip): fp32, one GPU.  Refused here, before any device work."""
+        c = self.config
+        if self.is_pixel or len(tuple(c.hidden_dims)) != 1:
+            return
+        if self.world_size > 1:
+            raise ValueError(f"model_id {c.model_id!r} has one hidden layer: its update has no gradient exchange, "
+                             f"world_size={self.world_size} is not supported (use one GPU)")
+        if str(getattr(c, "precision", "fp32")) == "bf16":
+            raise ValueError(f"model_id {c.model_id!r} has one hidden layer: its update is fp32 only, "
+                             "precision 'bf16' is a mode of the two-hidden-layer chain")
+
     def build_env(self, stage: str, env=None):
         """BaseAgent.build_env (base_agent.py:129-192): the env the config names.  A passed env
         (the host VectorEnv build_env_from_config returns, or a device env) is used as is;
@@ -129,6 +143,15 @@ class DevicePPOAgent:
             return DeviceMountainCarVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
                                            max_steps=int(c.max_episode_steps or 200),
                                            wrappers=list(c.env_wrappers or ()), device=self.device)
+        if kind in TABULAR_KINDS:
+            tab = resolve_tabular_env(c)
+            if self.is_pixel or tab is None or tab["kind"] != kind:
+                raise ValueError(f"env_dynamics={kind!r} needs env_id FrozenLake-v1 / Taxi-v3 with exactly the "
+                                 "DiscreteEncoder wrapper (gsamd.config.resolve_tabular_env)")
+            return DeviceTabularVecEnv(c.n_envs, kind=kind, encoding=tab["encoding"], map_name=tab["map_name"],
+                                       is_slippery=tab["is_slippery"], seed=c.seed_train if train else c.seed_val,
+                                       env_offset=off, max_steps=int(c.max_episode_steps or 0) or None,
+                                       device=self.device)
         seed = c.seed if train else c.seed + 1000
         if self.is_pixel:
             return DeviceAtariVecEnv(n_envs=c.n_envs, n_actions=c.resolved_n_actions(), episode_len=c.episode_len,
@@ -631,7 +654,9 @@ class DevicePPOAgent:
     def activation_keys(self):
         if self.global_mode or not self.track_stats:
             return ()
-        layers = self.CNN_ACTIVATION_LAYERS if self.is_pixel else ("backbone.0", "backbone.2")
+        # the MLP's hooked layers: one Linear per hidden layer (backbone.0[, backbone.2])
+        layers = self.CNN_ACTIVATION_LAYERS if self.is_pixel else tuple(
+            f"backbone.{2 * i}" for i in range(len(tuple(self.config.hidden_dims))))
         return tuple(f"opt/activations/{n}/{k}" for n in layers for k in ("mean", "std", "dead_pct", "dead_max"))
 
     def global_shares(self, epoch: int) -> np.ndarray:
@@ -783,7 +808,9 @@ def build_agent(config, *args, **kwargs):
     """agents/__init__.py:1-8 for the device path.  Accepts a gsamd PPOConfig or the
     reference's own Config object (adapted by name, gsamd.config.from_reference_config).
     The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1, Acrobot-v1 and
-    MountainCar-v0 (with its reward shaper / state-count bonus wrappers) step on their device dynamics; any other env_id needs env= / env_factory= (the host VectorEnv
+    MountainCar-v0 (with its reward shaper / state-count bonus wrappers) step on their device dynamics,
+    FrozenLake-v1 and Taxi-v3 (with their DiscreteEncoder) on the device tabular env; any other env_id
+    needs env= / env_factory= (the host VectorEnv
     the reference's build_env_from_config returns); the synthetic env only with
     env_dynamics='synthetic'."""
     from .config import from_reference_config

@@ -5,7 +5,8 @@ from config/environments/{CartPole-v1,LunarLander-v3,Acrobot-v1,ALE-Pong-v5,ALE-
 through utils/config.py; tests/golden/configs.json, config_acrobot.json for Acrobot-v1:ppo and
 config_mountaincar.json for the three MountainCar-v0 variants are the machine-generated records
 the tests compare against).  The reference leaves MountainCar-v0's n_envs at "auto", the host's core
-count (utils/config.py:482-485): the record keeps "auto" and the presets take 32.  MODEL_REGISTRY
+count (utils/config.py:482-485): the record keeps "auto" and the presets take 32; the same holds for
+FrozenLake-v1's ppo / ppo_deterministic and Taxi-v3's ppo (config_toytext.json).  MODEL_REGISTRY
 mirrors utils/model_registry.py:17-76.
 """
 
@@ -60,6 +61,29 @@ PRESETS = {
            ("ppo", "MountainCar-v0_curiosity", [dict(_MC_CURIOSITY)]),
            ("ppo_rewardshaped", "MountainCar-v0_rewardshaped", [dict(_MC_SHAPER)]),
            ("ppo_curiosity", "MountainCar-v0_curiosity", [dict(_MC_CURIOSITY)]))},
+    # FrozenLake-v1 / Taxi-v3 (config/environments/{FrozenLake-v1,Taxi-v3}.yaml; record:
+    # tests/golden/config_toytext.json): Discrete observations through the reference's DiscreteEncoder,
+    # mlp_tiny (one hidden layer of 64).  n_envs resolves to "auto" there as for MountainCar-v0: 32 here.
+    # The spec names the state count (`n`), not a shape: resolved_obs_dim() follows the encoder.
+    **{f"FrozenLake-v1:{variant}": dict(
+        _COMMON, env_id="FrozenLake-v1", project_id=project, n_envs=32, n_steps=2048, batch_size=64,
+        n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, policy_lr=0.0003,
+        model_id="mlp_tiny", max_env_steps=None, obs_type="vector", accelerator="cpu",
+        env_kwargs={"is_slippery": slippery, "map_name": "4x4"},
+        env_wrappers=[{"id": "DiscreteEncoder", "encoding": "array"}],
+        spec={"action_space": {"discrete": 4},
+              "observation_space": {"default": "grid_4x4", "variants": {"grid_4x4": {"n": 16, "dtype": "int64"},
+                                                                        "grid_8x8": {"n": 64, "dtype": "int64"}}}})
+       for variant, project, slippery in (("ppo", "FrozenLake-v1", True),
+                                          ("ppo_deterministic", "FrozenLake-v1_deterministic", False))},
+    "Taxi-v3:ppo": dict(
+        _COMMON, env_id="Taxi-v3", project_id="Taxi-v3", n_envs=32, n_steps=1024, batch_size=64, n_epochs=20,
+        gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.01, policy_lr=0.01, model_id="mlp_tiny",
+        max_env_steps=10000000.0, obs_type="vector", accelerator="cpu",
+        env_wrappers=[{"id": "DiscreteEncoder", "encoding": "array"}],
+        spec={"action_space": {"discrete": 6},
+              "observation_space": {"default": "encoded_state",
+                                    "variants": {"encoded_state": {"n": 500, "dtype": "int64"}}}}),
     "ALE-Pong-v5:rgb_ppo": dict(
         _COMMON, env_id="ALE/Pong-v5", project_id="ALE-Pong-v5_rgb", n_envs=32, n_steps=256, batch_size=1024,
         n_epochs=15, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.01, policy_lr=0.0003,

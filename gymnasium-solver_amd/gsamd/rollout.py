@@ -30,8 +30,9 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import (GS_ENV_ACROBOT, GS_ENV_CARTPOLE, GS_ENV_MOUNTAINCAR, GS_MC_BONUS_TYPES, GS_MC_WRAP_BONUS,
-                   GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER, MountainCarWrappers, check, lib, ptr, stream_handle)
+from ._lib import (GS_ENCODINGS, GS_ENV_ACROBOT, GS_ENV_CARTPOLE, GS_ENV_MOUNTAINCAR, GS_MC_BONUS_TYPES,
+                   GS_MC_WRAP_BONUS, GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER, MountainCarWrappers, TabularSpec, check, lib,
+                   ptr, stream_handle)
 from .config import resolve_mountaincar_wrappers
 from .distributed import allreduce_sum_f64
 from .rollout_stats import RollingWindow
@@ -226,6 +227,66 @@ class DeviceMountainCarVecEnv:
                                       self.max_steps, self.seed, self.env_offset, ptr(rewards_row), ptr(dones_row),
                                       ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
                                       ptr(self.ep_len_sum), stream_handle()), "gs_mountaincar_step")
+
+
+class DeviceTabularVecEnv:
+    """A tabular env on device (csrc/gs_tabular.hip): FrozenLake-v1 (`kind` "frozenlake", 4x4 or
+    8x8, slippery or not) or Taxi-v3 ("taxi") on gsamd.toytext's tables, or any (next, reward,
+    term, starts, n_states, n_actions, K) passed as `tables`.  The observation is the reference's
+    DiscreteEncoder (`encoding` array / binary / onehot) of the state, as float32.  NEXT_STEP
+    autoreset, TimeLimit `max_steps` (default: the registered id's, 100 / 200).  The tables are
+    uploaded once, here.  No env_kind: a one-hidden-layer policy has no one-launch rollout, the
+    collector replays its step graph.  Parity with gymnasium's own episodes is unpinned (the
+    outcome and reset draws use the counter hash, not PCG64)."""
+
+    device_native = True
+
+    def __init__(self, n_envs, kind="frozenlake", encoding="binary", map_name="4x4", is_slippery=True, seed=42,
+                 env_offset=0, max_steps=None, tables=None, device="cuda", **_):
+        from . import toytext
+        from .config import discrete_encoding_dim
+        if encoding not in GS_ENCODINGS:
+            raise ValueError(f"encoding must be one of {tuple(GS_ENCODINGS)}, got {encoding!r}")
+        nxt, rew, term, starts, S, A, K = tables if tables is not None else toytext.tables_for(
+            kind, map_name, bool(is_slippery))
+        self.kind, self.encoding = str(kind), str(encoding)
+        self.num_envs, self.n_states, self.n_actions, self.n_outcomes = int(n_envs), int(S), int(A), int(K)
+        self.obs_dim = discrete_encoding_dim(self.encoding, self.n_states)
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        self.max_steps = int(max_steps if max_steps else toytext.MAX_EPISODE_STEPS.get(self.kind, 100))
+        self.obs_shape, self.obs_dtype = (self.obs_dim,), torch.float32
+        self.device = torch.device(device)
+        N, z = self.num_envs, dict(device=self.device)
+        shape = (self.n_states, self.n_actions, self.n_outcomes)
+        self.next_table = torch.as_tensor(np.ascontiguousarray(nxt, np.int32).reshape(shape)).to(self.device)
+        self.reward_table = torch.as_tensor(np.ascontiguousarray(rew, np.float32).reshape(shape)).to(self.device)
+        self.term_table = torch.as_tensor(np.ascontiguousarray(term, np.uint8).reshape(shape)).to(self.device)
+        self.starts = torch.as_tensor(np.ascontiguousarray(starts, np.int32).reshape(-1)).to(self.device)
+        self.spec = TabularSpec(self.n_states, self.n_actions, self.n_outcomes, int(self.starts.numel()),
+                                GS_ENCODINGS[self.encoding], self.obs_dim)
+        self.state = torch.zeros(N, dtype=torch.int32, **z)
+        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
+        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
+        self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, **z)
+        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
+        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
+        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
+
+    def reset(self):
+        check(lib.gs_tabular_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
+                                   ptr(self.starts), self.num_envs, self.seed, self.env_offset, stream_handle()),
+              "gs_tabular_reset")
+        return self.obs, {}
+
+    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
+        if actions is None:
+            raise ValueError("a tabular env needs the step's actions")
+        check(lib.gs_tabular_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
+                                  ptr(self.next_table), ptr(self.reward_table), ptr(self.term_table),
+                                  ptr(self.starts), ptr(actions), self.num_envs, self.max_steps, self.seed,
+                                  self.env_offset, ptr(rewards_row), ptr(dones_row), ptr(timeouts_row),
+                                  ptr(self.ep_count), ptr(self.ep_ret_sum), ptr(self.ep_len_sum), stream_handle()),
+              "gs_tabular_step")
 
 
 class DeviceRolloutBuffer:

@@ -93,6 +93,25 @@ int gs_sampler_stream_i32(int64_t data_len, int64_t num_passes, uint64_t seed, i
 /* ---------------------------------------------------------------- MLP actor-critic
  * dims: obs_dim D, hidden H1, H2 (two ReLU layers, the reference's mlp_small/medium/
  * large presets; utils/model_registry.py:21-36), n_actions A.
+ *
+ * hidden2 == 0 means ONE hidden ReLU layer of hidden1 units (the reference's mlp_tiny preset).  The
+ * flat parameter vector is then backbone.0.weight[H][D], backbone.0.bias[H], policy_head.weight[A][H],
+ * policy_head.bias[A], value_head.weight[1][H], value_head.bias[1] — P = H D + H + A H + A + H + 1.
+ * Served by gs_mlp_param_count, gs_policy_scratch_bytes / _act / _value, gs_ppo_workspace_bytes,
+ * gs_ppo_update_workspace_bytes, gs_ppo_update, gs_ppo_minibatch_step, gs_ppo_loss and
+ * gs_mlp_activation_stats, in fp32 on one GPU; GS_E_INVALID from gs_ppo_stage, gs_ppo_update_global,
+ * gs_ppo_exchange_inside_bwd, gs_rollout_synth / _env / _mountaincar, with GS_HP_BF16 and with a
+ * communicator; gs_rollout_synth_supported / gs_rollout_env_supported answer 0.
+ * Its update (gs_ppo_update: every minibatch of the call in ONE launch of one 256-thread workgroup;
+ * use_graph is accepted and ignored) keeps the parameters, both Adam moments and the gradient in
+ * LDS, so the shape must satisfy, with P4 = P rounded up to 4 and A1 = A + 1:
+ *   obs_dim in [1, 64], n_actions in [1, 32], hidden1 a positive multiple of 16, and
+ *   10240 + 16 P4 + 4 (round4(32 D) + 64 H + round4(32 A1) + 160 + H) + 8192 <= 163840 bytes
+ * (reduction scratch; four parameter-sized vectors; a 32-row tile of observations, hidden
+ * activations and their gradients, head outputs and minibatch fields; the dead-neuron counts; the
+ * minibatch's row numbers and advantages, up to 1024 rows).
+ * 64-64-32 (6 305 parameters) needs 149 056 bytes.  Any other shape is GS_E_INVALID with the byte
+ * counts in the message.
  */
 typedef struct gs_mlp_dims {
     int32_t obs_dim;
@@ -541,6 +560,41 @@ int gs_rollout_mountaincar(const float *params_dev, gs_mlp_dims dims, int64_t N,
                            int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev,
                            float *obs_rows_dev, int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev,
                            float *reward_rows_dev, uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
+
+/* ---------------------------------------------------------------- tabular envs (FrozenLake-v1, Taxi-v3)
+ * Any finite MDP whose outcomes per (state, action) are n_outcomes equiprobable alternatives, as
+ * three read-only tables in HBM: next_dev i32 [S][A][K], reward_dev f32 [S][A][K], term_dev u8
+ * [S][A][K] (terminated).  gsamd/toytext.py restates gymnasium 1.x FrozenLake-v1 (4x4 / 8x8;
+ * slippery K = 3, else K = 1) and Taxi-v3 (K = 1) in this form; gymnasium's PCG64 stream is not
+ * reproduced, so parity with its own episodes is unpinned, as for the other device envs.
+ * state_dev: (N) i32; meta_dev (N, 3) i32 {steps, episodes, pending}; NEXT_STEP autoreset (a reset
+ * step only resets: reward 0, not done), TimeLimit max_steps, rows and episode counters as
+ * gs_cartpole_step.  Outcome of a step: k = min(K - 1, (int)(u K)), u in [0, 1) from the counter
+ * hash of (seed, env_offset + env, episode, step in episode) on a stream of its own; reset:
+ * starts_dev[min(n_starts - 1, (int)(u n_starts))] with u the reset hash of (seed, env_offset + env,
+ * episode), so trajectories do not depend on the launch geometry or on how env_offset partitions
+ * the envs.  Every table index is range-checked on device: an action outside [0, A) is clamped, a
+ * next state outside [0, S) ends the episode in place.
+ * obs_dev (N, obs_dim) f32 is the reference's gym_wrappers/discrete_encoder.py of the state:
+ * GS_ENC_ARRAY [(float)s] (the reference keeps int64 there; the MLP's input is its float32 value),
+ * GS_ENC_BINARY the max(1, ceil(log2 S)) bits LSB first, GS_ENC_ONEHOT the unit vector (S <= 64, the
+ * policy's obs_dim limit; GS_E_INVALID beyond).  spec.obs_dim must be the encoding's. */
+#define GS_ENC_ARRAY 0
+#define GS_ENC_BINARY 1
+#define GS_ENC_ONEHOT 2
+typedef struct gs_tabular_spec {
+    int32_t n_states, n_actions, n_outcomes;   /* K >= 1 */
+    int32_t n_starts;                          /* reset: uniform over starts_dev[0..n_starts) */
+    int32_t encoding;                          /* GS_ENC_ARRAY / GS_ENC_BINARY / GS_ENC_ONEHOT */
+    int32_t obs_dim;                           /* 1 / max(1, ceil(log2 n_states)) / n_states */
+} gs_tabular_spec;
+int gs_tabular_reset(int32_t *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, gs_tabular_spec spec,
+                     const int32_t *starts_dev, int64_t N, uint64_t seed, int64_t env_offset, void *stream);
+int gs_tabular_step(int32_t *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, gs_tabular_spec spec,
+                    const int32_t *next_dev, const float *reward_dev, const uint8_t *term_dev,
+                    const int32_t *starts_dev, const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed,
+                    int64_t env_offset, float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
+                    int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
 
 /* The fp32 MFMA GEMM under the CNN path (convolutions as GEMMs, fc, heads), exported for its
  * tests: row-major C[M][N] = op(A) op(B) + beta C (+ bias[n]) (ReLU if relu), op(X) = X^T
