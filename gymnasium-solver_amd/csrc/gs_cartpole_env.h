@@ -2,11 +2,14 @@
 // (gs_cartpole.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), so both produce the
 // same bits.  Both files compile with -ffp-contract=off.  Twin: oracle/cartpole_ref.py.
 // Also the pieces every device env with real dynamics shares: the counter hash of the reset
-// draws and the step's result.
+// draws and the step's result.  At the end: the reference's CartPoleV1_RewardShaper on top of the
+// same step (cartpole_phi, cartpole_shaped_env_step; twin tests/cartpole_shaper_twin.py).
 #pragma once
 
 #include <math.h>
 #include <stdint.h>
+
+#include "../../include/gsamd.h"   // gs_cartpole_wrappers
 
 namespace gs {
 
@@ -98,6 +101,58 @@ __device__ __forceinline__ EnvStepOut cartpole_env_step(CPState &s, int32_t (&me
     }
     meta[0] = steps;
     return EnvStepOut{1.0f, terminated || truncated, truncated};
+}
+
+// CartPoleV1_RewardShaper._phi (the reference's gym_wrappers/CartPoleV1/reward_shaper.py) on the
+// float32 observation's x and theta, in double as the class's float(obs[i]) arithmetic; the
+// thresholds are the env's own (x_threshold, theta_threshold_radians).  No shaper: 0.
+__device__ __forceinline__ double cartpole_phi(const gs_cartpole_wrappers &w, float x_obs, float theta_obs)
+{
+    if (!w.shaper) return 0.0;
+    const double theta_threshold = 12.0 * 2.0 * M_PI / 360.0, x_threshold = 2.4;
+    const double x = (double)x_obs, theta = (double)theta_obs;
+    double pos = 1.0 - fabs(x) / fmax(x_threshold, 1e-6);
+    double ang = 1.0 - fabs(theta) / fmax(theta_threshold, 1e-6);
+    if (w.clip_potential) {
+        pos = pos < 0.0 ? 0.0 : (pos > 1.0 ? 1.0 : pos);
+        ang = ang < 0.0 ? 0.0 : (ang > 1.0 ? 1.0 : ang);
+    }
+    return w.angle_reward_scale * ang + w.position_reward_scale * pos;
+}
+
+__device__ __forceinline__ double cartpole_phi(const gs_cartpole_wrappers &w, const CPState &s)
+{
+    return cartpole_phi(w, (float)s.x, (float)s.theta);
+}
+
+// One env's step under the shaper: cartpole_env_step's dynamics, flags, meta and reset hash, with
+// reward = (float)(1.0 + (phi - prev_phi)) and the running return adding that reward.  The
+// wrapper's reset() takes the reset observation's potential, so a NEXT_STEP autoreset row stays
+// reward 0 and re-arms prev_phi.
+__device__ __forceinline__ EnvStepOut cartpole_shaped_env_step(CPState &s, double &prev_phi, int32_t (&meta)[3],
+                                                               float &er, int64_t action, int max_steps,
+                                                               uint64_t seed, uint64_t ge,
+                                                               const gs_cartpole_wrappers &w, int32_t *ep_cnt,
+                                                               float *ep_ret_sum, float *ep_len_sum)
+{
+    const bool reset_row = meta[2] != 0;
+    float unshaped = 0.0f;     // the dynamics' own return accumulator is not this env's
+    const EnvStepOut so = cartpole_env_step(s, meta, unshaped, action, max_steps, seed, ge, nullptr, nullptr, nullptr);
+    const double phi = cartpole_phi(w, s);
+    if (reset_row) {
+        prev_phi = phi;
+        er = 0.0f;
+        return so;
+    }
+    const float reward = (float)(1.0 + (phi - prev_phi));
+    prev_phi = phi;
+    er = er + reward;
+    if (so.done) {
+        if (ep_cnt) *ep_cnt += 1;
+        if (ep_ret_sum) *ep_ret_sum += er;
+        if (ep_len_sum) *ep_len_sum += (float)meta[0];
+    }
+    return EnvStepOut{reward, so.done, so.timeout};
 }
 
 }  // namespace gs

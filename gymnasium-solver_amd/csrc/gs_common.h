@@ -322,6 +322,31 @@ int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mo
 const char *mountaincar_wrappers_error(const gs_mountaincar_wrappers &w, const void *counts);
 int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
                                uint64_t counter0, const MountainCarEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
+// CartPole under the reference's reward shaper (kind GS_ENV_CARTPOLE's shape): the same tensors
+// plus the wrapper's previous potential [N] and its parameters
+struct CartPoleShapedEnvArgs : DynEnvArgs {
+    double *prev_phi;
+    gs_cartpole_wrappers w;
+};
+int launch_rollout_cartpole_shaped(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                                   uint64_t counter0, const CartPoleShapedEnvArgs &ev, const RolloutRows &rw,
+                                   hipStream_t s);
+// Bandit-v0 (GS_ENV_BANDIT, obs dim == actions == n_arms): no state tensor
+struct BanditEnvArgs {
+    int32_t *meta;                   // [N][3] {steps, episodes, pending}
+    float *ep_ret, *obs;             // [N], [N][n_arms] (zeros)
+    int32_t *ep_cnt;                 // [N] finished-episode counters (may be null)
+    float *ep_ret_sum, *ep_len_sum;
+    int max_steps;
+    uint64_t seed;
+    int64_t env_offset;
+    gs_bandit_spec sp;
+};
+// null, or what is wrong with the spec: every bandit entry checks this before a launch, so no
+// index leaves the spec's arrays (gs_bandit.hip)
+const char *bandit_spec_error(const gs_bandit_spec &sp);
+int launch_rollout_bandit(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                          uint64_t counter0, const BanditEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
 
 inline int n_col_blocks(int H) { return (H + kTile - 1) / kTile; }
 inline int n_sumsq_slots(const Layout &L) { return n_col_blocks(L.H2) * n_col_blocks(L.H1) + 2 * n_col_blocks(L.H2) + 1; }

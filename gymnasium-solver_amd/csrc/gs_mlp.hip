@@ -46,6 +46,7 @@
 #include "gs_cartpole_env.h"
 #include "gs_acrobot_env.h"
 #include "gs_mountaincar_env.h"
+#include "gs_bandit_env.h"
 
 namespace gs {
 
@@ -1212,6 +1213,68 @@ struct RolloutMountainCarEnv : RolloutDynEnvBase<MCState, 2> {
     }
 };
 
+// CartPole under the reference's reward shaper: its own Args (the previous potentials and the
+// wrapper's parameters ride behind DynEnvArgs); thread `me` keeps its env's previous potential in a
+// register for the whole launch.
+struct RolloutCartPoleShapedEnv : RolloutDynEnvBase<CPState, 4> {
+    using Args = CartPoleShapedEnvArgs;
+    using Base = RolloutDynEnvBase<CPState, 4>;
+    double prev_phi;
+    __device__ __forceinline__ void load(const Args &ev, int64_t me)
+    {
+        Base::load(ev, me);
+        prev_phi = ev.prev_phi[me];
+    }
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        return cartpole_shaped_env_step(s, prev_phi, meta, er, action, ev.max_steps, ev.seed,
+                                        (uint64_t)(ev.env_offset + me), ev.w, ev.ep_cnt ? ev.ep_cnt + me : nullptr,
+                                        ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
+                                        ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+    }
+    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
+                                             bool env_thread) const
+    {
+        if (env_thread) cartpole_write_obs(s, xs + 4 * tid);
+    }
+    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
+    {
+        Base::store(ev, me);
+        ev.prev_phi[me] = prev_phi;
+    }
+};
+
+// Bandit-v0: no state beyond meta and the running return; the observation rows stay zero
+struct RolloutBanditEnv {
+    using Args = BanditEnvArgs;
+    int32_t meta[3];
+    float er;
+    __device__ __forceinline__ void load(const Args &ev, int64_t me)
+    {
+        meta[0] = ev.meta[3 * me + 0];
+        meta[1] = ev.meta[3 * me + 1];
+        meta[2] = ev.meta[3 * me + 2];
+        er = ev.ep_ret[me];
+    }
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        return bandit_env_step(meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me), ev.sp,
+                               ev.ep_cnt ? ev.ep_cnt + me : nullptr, ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
+                               ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
+    }
+    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int D, int, int tid, bool) const
+    {
+        for (int u = tid; u < kTile * D; u += 256) xs[u] = 0.0f;
+    }
+    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
+    {
+        ev.meta[3 * me + 0] = meta[0];
+        ev.meta[3 * me + 1] = meta[1];
+        ev.meta[3 * me + 2] = meta[2];
+        ev.ep_ret[me] = er;
+    }
+};
+
 size_t rollout_synth_lds_bytes(const Layout &L)
 {
     const int A1 = L.A + 1, ncb = (L.H2 + kTile - 1) / kTile;
@@ -1430,6 +1493,8 @@ bool rollout_env_fits(const Layout &L, int kind)
     if (kind == GS_ENV_CARTPOLE) return L.D == 4 && L.A == 2 && rollout_synth_fits(L);
     if (kind == GS_ENV_ACROBOT) return L.D == 6 && L.A == 3 && rollout_synth_fits(L);
     if (kind == GS_ENV_MOUNTAINCAR) return L.D == 2 && L.A == 3 && rollout_synth_fits(L);
+    if (kind == GS_ENV_BANDIT)
+        return L.D == L.A && L.A >= 2 && L.A <= GS_BANDIT_ROLLOUT_MAX_ARMS && rollout_synth_fits(L);
     return false;
 }
 
@@ -1450,6 +1515,28 @@ int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T
     GS_REQUIRE(rollout_env_fits(L, GS_ENV_MOUNTAINCAR),
                "gs_rollout_mountaincar: the policy is not MountainCar's (obs dim 2, 3 actions) or does not fit in LDS");
     return launch_rollout_sh<ShapeR<4>, RolloutMountainCarEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
+}
+
+int launch_rollout_cartpole_shaped(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                                   uint64_t counter0, const CartPoleShapedEnvArgs &ev, const RolloutRows &rw,
+                                   hipStream_t s)
+{
+    GS_REQUIRE(rollout_env_fits(L, GS_ENV_CARTPOLE),
+               "gs_rollout_cartpole_shaped: the policy is not CartPole's (obs dim 4, 2 actions) or does not fit in LDS");
+    return launch_rollout_sh<ShapeR<4>, RolloutCartPoleShapedEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
+}
+
+// The bandit's policy has n_arms actions: a 10-action runtime shape serves the reference's 10 arms
+// (head_act_row's sums run over a < A in order, so its rows equal gs_policy_act's 32-action shape);
+// more arms take the step loop
+int launch_rollout_bandit(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
+                          uint64_t counter0, const BanditEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
+{
+    GS_REQUIRE(rollout_env_fits(L, GS_ENV_BANDIT) && L.A == ev.sp.n_arms,
+               "gs_rollout_bandit: the policy is not the bandit's (obs dim = actions = n_arms <= %d) or does not fit "
+               "in LDS", GS_BANDIT_ROLLOUT_MAX_ARMS);
+    return launch_rollout_sh<ShapeR<GS_BANDIT_ROLLOUT_MAX_ARMS>, RolloutBanditEnv>(P, L, N, T, mode, rng_seed,
+                                                                                    counter0, ev, rw, s);
 }
 
 // ------------------------------------------------------------------------------------

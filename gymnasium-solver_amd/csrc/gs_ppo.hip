@@ -196,6 +196,7 @@ extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, 
     GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_env: mode %d not in {0,1,2}", mode);
     GS_REQUIRE(kind != GS_ENV_MOUNTAINCAR,
                "gs_rollout_env: MountainCar takes its count tables and wrappers through gs_rollout_mountaincar");
+    GS_REQUIRE(kind != GS_ENV_BANDIT, "gs_rollout_env: the bandit takes its spec through gs_rollout_bandit");
     GS_REQUIRE(kind == GS_ENV_CARTPOLE || kind == GS_ENV_ACROBOT,
                "gs_rollout_env: env kind %d has no dynamics here (the synthetic env: gs_rollout_synth)", kind);
     GS_REQUIRE(max_steps > 0, "gs_rollout_env: max_steps must be > 0");
@@ -237,6 +238,59 @@ extern "C" int gs_rollout_mountaincar(const float *params, gs_mlp_dims dims, int
     RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
     return launch_rollout_mountaincar(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
                                       (hipStream_t)stream);
+}
+
+extern "C" int gs_rollout_cartpole_shaped(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                          uint64_t rng_seed, uint64_t rng_counter0, double *env_state,
+                                          double *env_prev_phi, int32_t *env_meta, float *env_ep_ret, float *env_obs,
+                                          gs_cartpole_wrappers wrappers, int32_t max_steps, uint64_t env_seed,
+                                          int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum,
+                                          float *ep_len_sum, float *obs_rows, int64_t *action_rows, float *logp_rows,
+                                          float *value_rows, float *reward_rows, uint8_t *done_rows,
+                                          uint8_t *timeout_rows, void *stream)
+{
+    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_cartpole_shaped");
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_cartpole_shaped: bad N / T");
+    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_cartpole_shaped: mode %d not in {0,1,2}", mode);
+    GS_REQUIRE(max_steps > 0, "gs_rollout_cartpole_shaped: max_steps must be > 0");
+    GS_REQUIRE(params && env_state && env_prev_phi && env_meta && env_ep_ret && env_obs && obs_rows && action_rows &&
+                   logp_rows && value_rows && reward_rows && done_rows && timeout_rows,
+               "gs_rollout_cartpole_shaped: null buffer");
+    if (T == 0) return GS_OK;
+    CartPoleShapedEnvArgs ev{{env_state, env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum,
+                              max_steps, env_seed, env_offset},
+                             env_prev_phi, wrappers};
+    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return launch_rollout_cartpole_shaped(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
+                                          (hipStream_t)stream);
+}
+
+extern "C" int gs_rollout_bandit(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                 uint64_t rng_seed, uint64_t rng_counter0, int32_t *env_meta, float *env_ep_ret,
+                                 float *env_obs, gs_bandit_spec spec, int32_t max_steps, uint64_t env_seed,
+                                 int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum, float *ep_len_sum,
+                                 float *obs_rows, int64_t *action_rows, float *logp_rows, float *value_rows,
+                                 float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows, void *stream)
+{
+    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_bandit");
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_bandit: bad N / T");
+    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_bandit: mode %d not in {0,1,2}", mode);
+    GS_REQUIRE(max_steps > 0, "gs_rollout_bandit: max_steps must be > 0");
+    GS_REQUIRE(params && env_meta && env_ep_ret && env_obs && obs_rows && action_rows && logp_rows && value_rows &&
+                   reward_rows && done_rows && timeout_rows,
+               "gs_rollout_bandit: null buffer");
+    const char *bad = bandit_spec_error(spec);
+    GS_REQUIRE(!bad, "gs_rollout_bandit: %s", bad);
+    if (T == 0) return GS_OK;
+    BanditEnvArgs ev{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps, env_seed,
+                     env_offset, spec};
+    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return launch_rollout_bandit(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
+                                 (hipStream_t)stream);
 }
 
 extern "C" int gs_policy_value(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, float *value,

@@ -20,6 +20,7 @@ GS_ABI_VERSION = 7          # include/gsamd.h: the argument lists this binding d
 GS_NUM_METRICS = 40
 GS_ENV_SYNTHETIC, GS_ENV_CARTPOLE, GS_ENV_ACROBOT = 0, 1, 2     # include/gsamd.h: gs_rollout_env kinds
 GS_ENV_MOUNTAINCAR = 3      # answered by gs_rollout_env_supported; rolled out by gs_rollout_mountaincar
+GS_ENV_BANDIT = 4           # answered by gs_rollout_env_supported; rolled out by gs_rollout_bandit
 GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER, GS_MC_WRAP_BONUS = 0, 1, 2
 GS_MC_BONUS_TYPES = {"count": 0, "inverse": 1, "log": 2}       # GS_MC_BONUS_*
 METRIC_SLOTS = (
@@ -46,6 +47,22 @@ class MountainCarWrappers(ctypes.Structure):
                 ("velocity_reward_scale", ctypes.c_double), ("height_reward_scale", ctypes.c_double),
                 ("position_bins", ctypes.c_int32), ("velocity_bins", ctypes.c_int32),
                 ("bonus_type", ctypes.c_int32), ("min_count", ctypes.c_int32), ("bonus_scale", ctypes.c_double)]
+
+
+class CartPoleWrappers(ctypes.Structure):
+    """gs_cartpole_wrappers (include/gsamd.h): the CartPoleV1_RewardShaper's parameters."""
+    _fields_ = [("shaper", ctypes.c_int32), ("clip_potential", ctypes.c_int32),
+                ("angle_reward_scale", ctypes.c_double), ("position_reward_scale", ctypes.c_double)]
+
+
+GS_BANDIT_MAX_ARMS = 32             # include/gsamd.h
+GS_BANDIT_ROLLOUT_MAX_ARMS = 10     # the one-launch rollout's bound; more arms take the step loop
+
+
+class BanditSpec(ctypes.Structure):
+    """gs_bandit_spec (include/gsamd.h): the arms' float32 means and stds, by value."""
+    _fields_ = [("n_arms", ctypes.c_int32), ("episode_length", ctypes.c_int32),
+                ("means", ctypes.c_float * GS_BANDIT_MAX_ARMS), ("stds", ctypes.c_float * GS_BANDIT_MAX_ARMS)]
 
 
 GS_ENCODINGS = {"array": 0, "binary": 1, "onehot": 2}          # GS_ENC_*
@@ -162,6 +179,16 @@ def _load():
         "gs_rollout_mountaincar": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
                                                   MountainCarWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                                   vp, vp, vp]),
+        "gs_cartpole_shaped_reset": (ctypes.c_int, [vp, vp, vp, vp, vp, CartPoleWrappers, i64, u64, i64, vp]),
+        "gs_cartpole_shaped_step": (ctypes.c_int, [vp, vp, vp, vp, vp, CartPoleWrappers, vp, i64, i32, u64, i64, vp, vp,
+                                                   vp, vp, vp, vp, vp]),
+        "gs_rollout_cartpole_shaped": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
+                                                      CartPoleWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp,
+                                                      vp, vp, vp, vp]),
+        "gs_bandit_reset": (ctypes.c_int, [vp, vp, vp, BanditSpec, i64, vp]),
+        "gs_bandit_step": (ctypes.c_int, [vp, vp, vp, BanditSpec, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_rollout_bandit": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, BanditSpec,
+                                             i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gs_tabular_reset": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, i64, u64, i64, vp]),
         "gs_tabular_step": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp,
                                            vp, vp, vp, vp, vp]),
@@ -208,7 +235,9 @@ EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_norma
             "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
             "gs_cnn_ppo_update_global",
             "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",
-            "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar", "gs_tabular_reset", "gs_tabular_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
+            "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar",
+            "gs_cartpole_shaped_reset", "gs_cartpole_shaped_step", "gs_rollout_cartpole_shaped", "gs_bandit_reset",
+            "gs_bandit_step", "gs_rollout_bandit", "gs_tabular_reset", "gs_tabular_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
             "gs_comm_init", "gs_comm_xgmi_create", "gs_comm_xgmi_connect", "gs_comm_status", "gs_comm_error_record",
             "gs_comm_xgmi_set_colocation", "gs_comm_xgmi_set_bwd_exchange", "gs_comm_xgmi_reset",
             "gs_comm_allreduce_mean_f32", "gs_comm_allreduce_sum_f64", "gs_ppo_global_adv_stats",

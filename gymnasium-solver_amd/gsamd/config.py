@@ -77,6 +77,7 @@ class PPOConfig:
     #   "mountaincar" device MountainCar-v0 dynamics with the config's env_wrappers
     #   "frozenlake" / "taxi" the device tabular env on gsamd.toytext's tables, with the config's
     #               DiscreteEncoder and (FrozenLake) map kwargs
+    #   "bandit"    the device Bandit-v0 with the config's env_kwargs (resolve_bandit_env)
     env_dynamics: str = "auto"
     # data-parallel semantics of a multi-rank update:
     #   "local"  every rank takes B-row minibatches of its own samples (weak scaling, global batch G·B)
@@ -169,6 +170,9 @@ class PPOConfig:
     def resolved_obs_dim(self) -> int:
         if self.obs_dim:
             return int(self.obs_dim)
+        bandit = resolve_bandit_env(self)
+        if bandit is not None:          # Bandit-v0 observes zeros(n_arms)
+            return int(bandit["n_arms"])
         obs = (self.spec or {}).get("observation_space", {})
         variants = obs.get("variants", {})
         default = variants.get(obs.get("default", "state"), {})
@@ -181,6 +185,8 @@ class PPOConfig:
             if enc and enc[-1].get("encoding", "binary") in DISCRETE_ENCODINGS:
                 return discrete_encoding_dim(enc[-1].get("encoding", "binary"), int(default["n"]))
         shape = default.get("shape") or [4]
+        if isinstance(shape[0], str):   # a symbolic length (Bandit-v0's [n_arms]): the env kwarg of that name
+            return int((self.env_kwargs or {})[shape[0]])
         return int(shape[0])
 
     def get_rollout_collector_kwargs(self) -> Dict[str, Any]:
@@ -193,12 +199,12 @@ class PPOConfig:
 _FIELDS = {f.name for f in dataclasses.fields(PPOConfig)}
 _ALIASES = {"LunarLander-v2": "LunarLander-v3"}
 
-ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi")
+ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi", "bandit")
 # env ids whose dynamics the device implements, as BaseAgent.build_env would build them from a
 # config without wrappers / env kwargs / observation normalisation; the two
 # tabular envs need exactly the DiscreteEncoder wrapper (resolve_tabular_env)
 DEVICE_DYNAMICS = {"CartPole-v1": "cartpole", "Acrobot-v1": "acrobot", "MountainCar-v0": "mountaincar",
-                   "FrozenLake-v1": "frozenlake", "Taxi-v3": "taxi"}
+                   "FrozenLake-v1": "frozenlake", "Taxi-v3": "taxi", "Bandit-v0": "bandit"}
 TABULAR_KINDS = ("frozenlake", "taxi")
 DISCRETE_ENCODINGS = ("array", "binary", "onehot")      # gym_wrappers/discrete_encoder.py
 MAX_POLICY_OBS_DIM = 64                                 # csrc/gs_common.h kMaxObsDim
@@ -314,14 +320,103 @@ def resolve_mountaincar_wrappers(wrappers) -> Optional[List[Tuple[str, Dict[str,
     return out
 
 
+# The one env_wrapper the device CartPole-v1 applies itself (csrc/gs_cartpole_env.h), with the
+# keyword arguments and defaults of the reference's class (gym_wrappers/CartPoleV1/reward_shaper.py:23-29)
+CARTPOLE_WRAPPERS = {
+    "CartPoleV1_RewardShaper": {"angle_reward_scale": 1.0, "position_reward_scale": 0.25, "clip_potential": True},
+}
+
+
+def resolve_cartpole_wrappers(wrappers) -> Optional[List[Tuple[str, Dict[str, Any]]]]:
+    """A config's env_wrappers list as [(id, keyword arguments with the reference's defaults filled
+    in)] when the device CartPole applies it: empty, or exactly one CartPoleV1_RewardShaper entry
+    carrying only the class's own keyword arguments, finite real scales and a bool clip_potential.
+    None for any other list (the host env then)."""
+    wrappers = list(wrappers or [])
+    if not wrappers:
+        return []
+    if len(wrappers) != 1 or not isinstance(wrappers[0], dict):
+        return None
+    w = wrappers[0]
+    wid = w.get("id")
+    if wid not in CARTPOLE_WRAPPERS:
+        return None
+    kw = dict(CARTPOLE_WRAPPERS[wid])
+    for k, v in w.items():
+        if k == "id":
+            continue
+        if k not in kw:
+            return None
+        kw[k] = v
+    if not (_is_real(kw["angle_reward_scale"]) and _is_real(kw["position_reward_scale"])):
+        return None
+    if not isinstance(kw["clip_potential"], bool):
+        return None
+    return [(wid, kw)]
+
+
+BANDIT_MAX_ARMS = 32               # include/gsamd.h GS_BANDIT_MAX_ARMS (csrc/gs_common.h kMaxActions)
+BANDIT_KWARGS = ("n_arms", "means", "stds", "episode_length")
+
+
+def bandit_arms(n_arms: int, means=None, stds=1.0):
+    """(means, stds) as the float32 lists MultiArmedBanditEnv keeps (gym_envs/mab_env.py:179-187):
+    means default to linspace(0, n_arms, n_arms) in float32, a scalar std is broadcast."""
+    import numpy as np
+    n = int(n_arms)
+    m = np.linspace(0, n, num=n, dtype=np.float32) if means is None else np.asarray(means, dtype=np.float32)
+    s = np.full(n, float(stds), dtype=np.float32) if isinstance(stds, (int, float)) else np.asarray(stds, np.float32)
+    return m, s
+
+
+def resolve_bandit_env(cfg) -> Optional[Dict[str, Any]]:
+    """What the device Bandit-v0 needs from a config, or None when the device does not build that
+    env (the host env then).  env_kwargs may hold only n_arms (an int in [2, 32] equal to the
+    spec's action count; default 10), means (None or n_arms finite reals), stds (a finite real
+    >= 0 or n_arms of them; default 1.0) and episode_length (an int >= 1; default 1) — a `seed`
+    key means the host env; no env_wrappers, no normalize_obs, no frame_stack.
+    Returns {n_arms, means, stds, episode_length} with means / stds float32 arrays."""
+    if DEVICE_DYNAMICS.get(str(getattr(cfg, "env_id", ""))) != "bandit":
+        return None
+    if getattr(cfg, "env_wrappers", None) or getattr(cfg, "normalize_obs", False):
+        return None
+    if getattr(cfg, "frame_stack", None) not in (None, 0, 1):
+        return None
+    kwargs = getattr(cfg, "env_kwargs", None) or {}
+    if not isinstance(kwargs, dict) or set(kwargs) - set(BANDIT_KWARGS):
+        return None
+    n_arms, length = kwargs.get("n_arms", 10), kwargs.get("episode_length", 1)
+    if not (_is_int(n_arms) and 2 <= n_arms <= BANDIT_MAX_ARMS and _is_int(length) and length >= 1):
+        return None
+    discrete = ((getattr(cfg, "spec", None) or {}).get("action_space") or {}).get("discrete")
+    if discrete is None or not _is_int(discrete) or int(discrete) != n_arms:
+        return None
+    means, stds = kwargs.get("means"), kwargs.get("stds", 1.0)
+    if means is not None:
+        if not isinstance(means, (list, tuple)) or len(means) != n_arms or not all(_is_real(v) for v in means):
+            return None
+    if isinstance(stds, (list, tuple)):
+        if len(stds) != n_arms or not all(_is_real(v) and v >= 0 for v in stds):
+            return None
+    elif not (_is_real(stds) and stds >= 0):
+        return None
+    m, s = bandit_arms(n_arms, means, stds)
+    import numpy as np
+    if not (np.isfinite(m).all() and np.isfinite(s).all()):      # finite as float32 too
+        return None
+    return dict(n_arms=int(n_arms), means=m, stds=s, episode_length=int(length))
+
+
 def device_env_kind(cfg) -> Optional[str]:
     """The device env a config trains on when the caller passes no env: "synthetic",
-    "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi", or None when the config names an env
-    the device does not simulate — the caller then passes the host VectorEnv the reference would build
-    (agents/base_agent.py:129-192 → utils/environment.py:421-425 build_env_from_config).
-    MountainCar-v0 may carry the env_wrappers the device applies itself
-    (resolve_mountaincar_wrappers), FrozenLake-v1 / Taxi-v3 carry exactly the DiscreteEncoder
-    (resolve_tabular_env); any wrapper on another env means the host env."""
+    "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi", "bandit", or None when the config
+    names an env the device does not simulate — the caller then passes the host VectorEnv the
+    reference would build (agents/base_agent.py:129-192 → utils/environment.py:421-425
+    build_env_from_config).  MountainCar-v0 and CartPole-v1 may carry the env_wrappers the device
+    applies itself (resolve_mountaincar_wrappers, resolve_cartpole_wrappers: CartPole-v1's
+    CartPoleV1_RewardShaper), FrozenLake-v1 / Taxi-v3 carry exactly the DiscreteEncoder
+    (resolve_tabular_env), Bandit-v0 carries the env_kwargs of its arms (resolve_bandit_env); any
+    wrapper on another env means the host env."""
     mode = str(getattr(cfg, "env_dynamics", None) or "auto")
     if mode != "auto":
         return mode
@@ -333,8 +428,12 @@ def device_env_kind(cfg) -> Optional[str]:
         ok = (resolve_tabular_env(cfg) is not None and not getattr(cfg, "normalize_obs", False)
               and getattr(cfg, "frame_stack", None) in (None, 0, 1))
         return kind if ok else None
+    if kind == "bandit":            # Bandit-v0: the arms' env_kwargs are the env's own
+        return kind if resolve_bandit_env(cfg) is not None else None
     if kind == "mountaincar":
         unwrapped = resolve_mountaincar_wrappers(wrappers) is not None
+    elif kind == "cartpole":
+        unwrapped = resolve_cartpole_wrappers(wrappers) is not None
     else:
         unwrapped = not wrappers
     plain = (unwrapped and not getattr(cfg, "env_kwargs", None)
@@ -343,7 +442,10 @@ def device_env_kind(cfg) -> Optional[str]:
 
 
 def needs_host_env(cfg) -> bool:
-    """True when build_agent(cfg) needs env= (a gymnasium VectorEnv built on the host)."""
+    """True when build_agent(cfg) needs env= (a gymnasium VectorEnv built on the host).  False for
+    every reference config with vector observations and no Box2D / ALE / VizDoom / Retro
+    dependency: CartPole-v1 (ppo, ppo_rewardshaped), Acrobot-v1, MountainCar-v0, FrozenLake-v1,
+    Taxi-v3 and Bandit-v0 (device_env_kind)."""
     return device_env_kind(from_reference_config(cfg)) is None
 
 

@@ -26,11 +26,11 @@ import ctypes
 
 from ._lib import ACT_SLOT, GS_HP_ACT_STATS, GS_HP_BF16, GS_NUM_METRICS, M, PPOGlobal, PPOHparams, RolloutView, RolloutViewU8, check, lib, ptr, stream_handle
 from .atari_env import DeviceAtariVecEnv
-from .config import TABULAR_KINDS, device_env_kind, resolve_tabular_env
+from .config import TABULAR_KINDS, device_env_kind, resolve_bandit_env, resolve_tabular_env
 from .cnn import DeviceCNNActorCritic
 from .policy import DeviceMLPActorCritic
-from .rollout import (DeviceAcrobotVecEnv, DeviceCartPoleVecEnv, DeviceMountainCarVecEnv, DeviceRolloutCollector,
-                      DeviceSyntheticVecEnv, DeviceTabularVecEnv)
+from .rollout import (DeviceAcrobotVecEnv, DeviceBanditVecEnv, DeviceCartPoleVecEnv, DeviceMountainCarVecEnv,
+                      DeviceRolloutCollector, DeviceSyntheticVecEnv, DeviceTabularVecEnv)
 from .samplers import IndexStreamPrefetcher, MultiPassRandomSampler, index_stream, rank_share
 from .distributed import allreduce_sum_f64, broadcast_int, check_replicas, comm_status, world_active
 from . import distributed as _dist
@@ -38,6 +38,7 @@ from .metrics import NUM_SUMS, MetricsRecorder, ppo_keys, ppo_records
 from .schedules import SCHEDULABLE, build_schedulers
 
 STAGES = ("train",)
+BANDIT_MAX_TRAINABLE_ARMS = 15      # see _device_env: what the MLP update's forward staging covers
 
 
 class MinibatchIndices:
@@ -129,8 +130,25 @@ class DevicePPOAgent:
         if kind == "cartpole":
             if self.is_pixel or c.resolved_obs_dim() != 4 or c.resolved_n_actions() != 2:
                 raise ValueError("env_dynamics='cartpole' needs vector observations of dim 4 and 2 actions")
+            # every stage's env carries the config's reward shaper (the reference builds each from the same list)
             return DeviceCartPoleVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
-                                        max_steps=int(c.max_episode_steps or 500), device=self.device)
+                                        max_steps=int(c.max_episode_steps or 500),
+                                        wrappers=list(c.env_wrappers or ()), device=self.device)
+        if kind == "bandit":
+            b = resolve_bandit_env(c)
+            if self.is_pixel or b is None or c.resolved_n_actions() != b["n_arms"]:
+                raise ValueError("env_dynamics='bandit' needs env_id Bandit-v0 with env_kwargs the device applies "
+                                 "(gsamd.config.resolve_bandit_env)")
+            if b["n_arms"] > BANDIT_MAX_TRAINABLE_ARMS:
+                # the env kernels take 32 arms; the two-hidden-layer update does not yet (measured at 20 arms:
+                # NaN / inf losses).  Its forward stages a 16-row tile's observations and the 16 x (A + 1) head
+                # weights with one element per thread of 256: complete only for obs_dim <= 16, n_actions <= 15.
+                raise ValueError(f"Bandit-v0 with n_arms={b['n_arms']}: the MLP update serves obs_dim <= 16 and "
+                                 f"n_actions <= 15, so at most {BANDIT_MAX_TRAINABLE_ARMS} arms train on the device")
+            return DeviceBanditVecEnv(c.n_envs, n_arms=b["n_arms"], means=b["means"], stds=b["stds"],
+                                      episode_length=b["episode_length"],
+                                      seed=c.seed_train if train else c.seed_val, env_offset=off,
+                                      max_steps=int(c.max_episode_steps or 0) or None, device=self.device)
         if kind == "acrobot":
             if self.is_pixel or c.resolved_obs_dim() != 6 or c.resolved_n_actions() != 3:
                 raise ValueError("env_dynamics='acrobot' needs vector observations of dim 6 and 3 actions")
@@ -807,8 +825,9 @@ class DevicePPOAgent:
 def build_agent(config, *args, **kwargs):
     """agents/__init__.py:1-8 for the device path.  Accepts a gsamd PPOConfig or the
     reference's own Config object (adapted by name, gsamd.config.from_reference_config).
-    The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1, Acrobot-v1 and
-    MountainCar-v0 (with its reward shaper / state-count bonus wrappers) step on their device dynamics,
+    The env is the one the config names (DevicePPOAgent.build_env): CartPole-v1 (with its reward
+    shaper), Acrobot-v1, MountainCar-v0 (with its reward shaper / state-count bonus wrappers) and
+    Bandit-v0 (with its arms' env_kwargs) step on their device dynamics,
     FrozenLake-v1 and Taxi-v3 (with their DiscreteEncoder) on the device tabular env; any other env_id
     needs env= / env_factory= (the host VectorEnv
     the reference's build_env_from_config returns); the synthetic env only with

@@ -6,7 +6,8 @@ through utils/config.py; tests/golden/configs.json, config_acrobot.json for Acro
 config_mountaincar.json for the three MountainCar-v0 variants are the machine-generated records
 the tests compare against).  The reference leaves MountainCar-v0's n_envs at "auto", the host's core
 count (utils/config.py:482-485): the record keeps "auto" and the presets take 32; the same holds for
-FrozenLake-v1's ppo / ppo_deterministic and Taxi-v3's ppo (config_toytext.json).  MODEL_REGISTRY
+FrozenLake-v1's ppo / ppo_deterministic and Taxi-v3's ppo (config_toytext.json) and for Bandit-v0's ppo
+(config_cartpole_bandit.json, which also records CartPole-v1:ppo_rewardshaped).  MODEL_REGISTRY
 mirrors utils/model_registry.py:17-76.
 """
 
@@ -38,6 +39,30 @@ PRESETS = {
         max_env_steps=100000.0, obs_type="vector", accelerator="cpu",
         spec={"action_space": {"discrete": 2}, "observation_space": {"default": "state",
                                                                      "variants": {"state": {"shape": [4]}}}}),
+    # the reward-shaped variant (config/environments/CartPole-v1.yaml:46-53, 83-87; record:
+    # tests/golden/config_cartpole_bandit.json): CartPole-v1:ppo under CartPoleV1_RewardShaper
+    "CartPole-v1:ppo_rewardshaped": dict(
+        _COMMON, env_id="CartPole-v1", project_id="CartPole-v1_rewardshaped", n_envs=8, n_steps=32, batch_size=256,
+        n_epochs=20, gamma=0.98, gae_lambda=0.8, clip_range=0.1, ent_coef=0.0, policy_lr=0.001,
+        model_id="mlp_medium", max_env_steps=100000.0, obs_type="vector", accelerator="cpu",
+        env_wrappers=[dict(id="CartPoleV1_RewardShaper", angle_reward_scale=1.0, position_reward_scale=0.25,
+                           clip_potential=True)],
+        spec={"action_space": {"discrete": 2}, "observation_space": {"default": "state",
+                                                                     "variants": {"state": {"shape": [4]}}}}),
+    # Bandit-v0 (config/environments/Bandit-v0.yaml:47-60; same record): the reference's stateless
+    # Gaussian bandit, the one classic config with a scheduled policy_lr (0.04 -> 0, linear over the
+    # whole budget).  n_envs resolves to "auto" there as for MountainCar-v0: 32 here.  The spec's
+    # observation shape is the symbol n_arms: resolved_obs_dim() follows env_kwargs.
+    "Bandit-v0:ppo": dict(
+        _COMMON, env_id="Bandit-v0", project_id="Bandit-v0", n_envs=32, n_steps=64, batch_size=64, n_epochs=4,
+        gamma=1.0, gae_lambda=1.0, clip_range=0.2, ent_coef=0.0, policy_lr=0.04, model_id="mlp_small",
+        max_env_steps=20000, obs_type="vector", accelerator="cpu",
+        env_kwargs={"n_arms": 10, "means": [0, 1, 2, 3, 4, 5, 6, 7, 8, 9], "stds": 1, "episode_length": 1},
+        schedules={"policy_lr": {"schedule": "linear", "start_value": 0.04, "end_value": 0.0, "start": 0.0,
+                                 "end": 1.0, "warmup": 0.0}},
+        spec={"action_space": {"discrete": 10},
+              "observation_space": {"default": "constant_zero",
+                                    "variants": {"constant_zero": {"shape": ["n_arms"], "dtype": "float32"}}}}),
     "LunarLander-v3:ppo": dict(
         _COMMON, env_id="LunarLander-v3", project_id="LunarLander-v3", n_envs=8, n_steps=2048, batch_size=64,
         n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, policy_lr=0.0003,

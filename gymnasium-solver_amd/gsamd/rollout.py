@@ -30,10 +30,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ._lib import (GS_ENCODINGS, GS_ENV_ACROBOT, GS_ENV_CARTPOLE, GS_ENV_MOUNTAINCAR, GS_MC_BONUS_TYPES,
-                   GS_MC_WRAP_BONUS, GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER, MountainCarWrappers, TabularSpec, check, lib,
-                   ptr, stream_handle)
-from .config import resolve_mountaincar_wrappers
+from ._lib import (GS_BANDIT_MAX_ARMS, GS_ENCODINGS, GS_ENV_ACROBOT, GS_ENV_BANDIT, GS_ENV_CARTPOLE,
+                   GS_ENV_MOUNTAINCAR, GS_MC_BONUS_TYPES, GS_MC_WRAP_BONUS, GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER,
+                   BanditSpec, CartPoleWrappers, MountainCarWrappers, TabularSpec, check, lib, ptr, stream_handle)
+from .config import bandit_arms, resolve_cartpole_wrappers, resolve_mountaincar_wrappers
 from .distributed import allreduce_sum_f64
 from .rollout_stats import RollingWindow
 
@@ -85,12 +85,27 @@ class DeviceCartPoleVecEnv:
     device_native = True
     env_kind = GS_ENV_CARTPOLE       # gs_rollout_env's kind: one-launch rollouts when the policy fits in LDS
 
-    def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, device="cuda", **_):
+    def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, wrappers=(), device="cuda", **_):
+        """`wrappers` is the config's env_wrappers list: empty, or the reference's
+        CartPoleV1_RewardShaper (CartPole-v1:ppo_rewardshaped), which the gs_cartpole_shaped_*
+        entries apply on the env's own thread with its previous potential in `prev_phi` (N) f64.
+        Without a shaper the env calls the unshaped entries and has no prev_phi."""
         self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 4, 2
         self.seed, self.env_offset, self.max_steps = int(seed), int(env_offset), int(max_steps)
         self.obs_shape, self.obs_dtype = (4,), torch.float32
         self.device = torch.device(device)
+        self.wrappers = [dict(w) for w in (wrappers or ())]
+        resolved = resolve_cartpole_wrappers(self.wrappers)
+        if resolved is None:
+            raise ValueError(f"the device CartPole-v1 does not apply env_wrappers={self.wrappers!r} "
+                             "(gsamd.config.resolve_cartpole_wrappers)")
+        self.wrappers_c, self.prev_phi = None, None
         N, z = self.num_envs, dict(device=self.device)
+        if resolved:
+            kw = resolved[0][1]
+            self.wrappers_c = CartPoleWrappers(1, int(kw["clip_potential"]), float(kw["angle_reward_scale"]),
+                                               float(kw["position_reward_scale"]))
+            self.prev_phi = torch.zeros(N, dtype=torch.float64, **z)
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)
         self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)
         self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
@@ -100,6 +115,11 @@ class DeviceCartPoleVecEnv:
         self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
 
     def reset(self):
+        if self.wrappers_c is not None:
+            check(lib.gs_cartpole_shaped_reset(ptr(self.state), ptr(self.prev_phi), ptr(self.meta), ptr(self.ep_ret),
+                                               ptr(self.obs), self.wrappers_c, self.num_envs, self.seed,
+                                               self.env_offset, stream_handle()), "gs_cartpole_shaped_reset")
+            return self.obs, {}
         check(lib.gs_cartpole_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.num_envs,
                                     self.seed, self.env_offset, stream_handle()), "gs_cartpole_reset")
         return self.obs, {}
@@ -107,6 +127,14 @@ class DeviceCartPoleVecEnv:
     def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
         if actions is None:
             raise ValueError("CartPole dynamics need the step's actions")
+        if self.wrappers_c is not None:
+            check(lib.gs_cartpole_shaped_step(ptr(self.state), ptr(self.prev_phi), ptr(self.meta), ptr(self.ep_ret),
+                                              ptr(self.obs), self.wrappers_c, ptr(actions), self.num_envs,
+                                              self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
+                                              ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count),
+                                              ptr(self.ep_ret_sum), ptr(self.ep_len_sum), stream_handle()),
+                  "gs_cartpole_shaped_step")
+            return
         check(lib.gs_cartpole_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), ptr(actions),
                                    self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
                                    ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
@@ -227,6 +255,64 @@ class DeviceMountainCarVecEnv:
                                       self.max_steps, self.seed, self.env_offset, ptr(rewards_row), ptr(dones_row),
                                       ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
                                       ptr(self.ep_len_sum), stream_handle()), "gs_mountaincar_step")
+
+
+class DeviceBanditVecEnv:
+    """Bandit-v0 on device (csrc/gs_bandit_env.h restates the reference's
+    gym_envs/mab_env.py MultiArmedBanditEnv): a stateless Gaussian bandit whose observation is
+    zeros(n_arms), reward mean[a] + std[a] z, terminated after episode_length steps, NEXT_STEP
+    autoreset; `max_steps` (a config's max_episode_steps) adds the TimeLimit, default
+    episode_length (the env's own spec).  means / stds as the class takes them (None: linspace(0,
+    n_arms, n_arms); a scalar std is broadcast), kept as float32.  There is no state tensor.
+    Parity with the reference's reward stream is unpinned (the normal draw is Box-Muller on the
+    counter hash, not numpy's PCG64 ziggurat)."""
+
+    device_native = True
+    env_kind = GS_ENV_BANDIT         # one-launch rollouts up to GS_BANDIT_ROLLOUT_MAX_ARMS arms
+    one_launch_max_envs = None
+
+    def __init__(self, n_envs, n_arms=10, means=None, stds=1.0, episode_length=1, seed=42, env_offset=0,
+                 max_steps=None, device="cuda", **_):
+        n = int(n_arms)
+        if not 2 <= n <= GS_BANDIT_MAX_ARMS:
+            raise ValueError(f"n_arms must be in [2, {GS_BANDIT_MAX_ARMS}], got {n_arms}")
+        if int(episode_length) < 1:
+            raise ValueError("episode_length must be >= 1")
+        m, s = bandit_arms(n, means, stds)
+        if m.shape != (n,) or s.shape != (n,):
+            raise ValueError("means / stds must have n_arms entries")
+        if not (np.isfinite(m).all() and np.isfinite(s).all() and (s >= 0).all()):
+            raise ValueError("means must be finite, stds finite and >= 0")
+        self.num_envs, self.obs_dim, self.n_actions, self.n_arms = int(n_envs), n, n, n
+        self.means, self.stds, self.episode_length = m, s, int(episode_length)
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        self.max_steps = int(max_steps if max_steps else episode_length)
+        self.obs_shape, self.obs_dtype = (n,), torch.float32
+        self.device = torch.device(device)
+        self.spec = BanditSpec()
+        self.spec.n_arms, self.spec.episode_length = n, self.episode_length
+        for a in range(n):
+            self.spec.means[a], self.spec.stds[a] = float(m[a]), float(s[a])
+        N, z = self.num_envs, dict(device=self.device)
+        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
+        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
+        self.obs = torch.zeros(N, n, dtype=torch.float32, **z)
+        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
+        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
+        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
+
+    def reset(self):
+        check(lib.gs_bandit_reset(ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, self.num_envs,
+                                  stream_handle()), "gs_bandit_reset")
+        return self.obs, {}
+
+    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
+        if actions is None:
+            raise ValueError("the bandit needs the step's actions")
+        check(lib.gs_bandit_step(ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, ptr(actions),
+                                 self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
+                                 ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
+                                 ptr(self.ep_len_sum), stream_handle()), "gs_bandit_step")
 
 
 class DeviceTabularVecEnv:
@@ -567,6 +653,22 @@ class DeviceRolloutCollector:
                 env.max_steps, env.seed, env.env_offset, ptr(env.ep_count), ptr(env.ep_ret_sum),
                 ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values),
                 ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_mountaincar")
+            return
+        if isinstance(env, DeviceCartPoleVecEnv) and env.wrappers_c is not None:     # the reward shaper rides along
+            check(lib.gs_rollout_cartpole_shaped(
+                ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed, self.total_vec_steps,
+                ptr(env.state), ptr(env.prev_phi), ptr(env.meta), ptr(env.ep_ret), ptr(env.obs), env.wrappers_c,
+                env.max_steps, env.seed, env.env_offset, ptr(env.ep_count), ptr(env.ep_ret_sum),
+                ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values),
+                ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_cartpole_shaped")
+            return
+        if isinstance(env, DeviceBanditVecEnv):
+            check(lib.gs_rollout_bandit(
+                ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed, self.total_vec_steps,
+                ptr(env.meta), ptr(env.ep_ret), ptr(env.obs), env.spec, env.max_steps, env.seed, env.env_offset,
+                ptr(env.ep_count), ptr(env.ep_ret_sum), ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions),
+                ptr(buf.logprobs), ptr(buf.values), ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts),
+                stream_handle()), "gs_rollout_bandit")
             return
         if not isinstance(env, DeviceSyntheticVecEnv):
             check(lib.gs_rollout_env(ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed,

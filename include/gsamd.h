@@ -171,6 +171,7 @@ int gs_rollout_synth(const float *params_dev, gs_mlp_dims dims, int64_t N, int64
 #define GS_ENV_CARTPOLE 1
 #define GS_ENV_ACROBOT 2
 #define GS_ENV_MOUNTAINCAR 3   /* answered by gs_rollout_env_supported; its rollout entry is gs_rollout_mountaincar */
+#define GS_ENV_BANDIT 4        /* answered by gs_rollout_env_supported; its rollout entry is gs_rollout_bandit */
 int gs_rollout_env_supported(gs_mlp_dims dims, int kind, int *supported_host);
 int gs_rollout_env(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
                    uint64_t rng_counter0, int kind, double *env_state_dev, int32_t *env_meta_dev,
@@ -494,6 +495,78 @@ int gs_cartpole_step(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, fl
                      const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed, int64_t env_offset,
                      float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
                      int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
+
+/* CartPole-v1 under the reference's CartPoleV1_RewardShaper (gym_wrappers/CartPoleV1/
+ * reward_shaper.py:23-77), the env of CartPole-v1:ppo_rewardshaped.  Dynamics, termination,
+ * truncation, counters and reset hash are gs_cartpole_step's; only the reward and what the
+ * episode-return accumulator adds change.  In double, on the float32 observation {x, theta}:
+ *   pos = 1 - |x| / max(2.4, 1e-6), ang = 1 - |theta| / max(12 * 2 pi / 360, 1e-6), both clipped
+ *   to [0, 1] with clip_potential; phi = angle_reward_scale * ang + position_reward_scale * pos;
+ *   reward = (float)(1.0 + (phi - prev_phi)); prev_phi = phi.
+ * prev_phi_dev: (N) f64, the potential of the observation the wrapper last saw; the reset entry
+ * and a NEXT_STEP autoreset row (reward 0) set it to phi(reset observation).  shaper == 0: no
+ * shaping (reward 1).  state_dev stays (N, 4) f64. */
+typedef struct gs_cartpole_wrappers {
+    int32_t shaper;                 /* 1: CartPoleV1_RewardShaper */
+    int32_t clip_potential;
+    double angle_reward_scale, position_reward_scale;
+} gs_cartpole_wrappers;
+int gs_cartpole_shaped_reset(double *state_dev, double *prev_phi_dev, int32_t *meta_dev, float *ep_ret_dev,
+                             float *obs_dev, gs_cartpole_wrappers wrappers, int64_t N, uint64_t seed,
+                             int64_t env_offset, void *stream);
+int gs_cartpole_shaped_step(double *state_dev, double *prev_phi_dev, int32_t *meta_dev, float *ep_ret_dev,
+                            float *obs_dev, gs_cartpole_wrappers wrappers, const int64_t *actions_dev, int64_t N,
+                            int32_t max_steps, uint64_t seed, int64_t env_offset, float *rewards_row_dev,
+                            uint8_t *dones_row_dev, uint8_t *timeouts_row_dev, int32_t *ep_done_count_dev,
+                            float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
+/* gs_rollout_env for the shaped CartPole (gs_rollout_env_supported's kind GS_ENV_CARTPOLE answers
+ * for it: obs dim 4, 2 actions): bit for bit T calls of gs_policy_act + gs_cartpole_shaped_step,
+ * prev_phi included. */
+int gs_rollout_cartpole_shaped(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                               uint64_t rng_seed, uint64_t rng_counter0, double *env_state_dev,
+                               double *env_prev_phi_dev, int32_t *env_meta_dev, float *env_ep_ret_dev,
+                               float *env_obs_dev, gs_cartpole_wrappers wrappers, int32_t max_steps,
+                               uint64_t env_seed, int64_t env_offset, int32_t *ep_done_count_dev,
+                               float *ep_ret_sum_dev, float *ep_len_sum_dev, float *obs_rows_dev,
+                               int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev,
+                               float *reward_rows_dev, uint8_t *done_rows_dev, uint8_t *timeout_rows_dev,
+                               void *stream);
+
+/* ---------------------------------------------------------------- Bandit-v0 (f1)
+ * The reference's gym_envs/mab_env.py MultiArmedBanditEnv on device: a stateless Gaussian
+ * multi-armed bandit.  obs_dev (N, n_arms) f32 is all zeros, on reset and after every step;
+ * actions in [0, n_arms) (an action outside is clamped into the range); reward =
+ * (float)((double)means[a] + (double)stds[a] * z); terminated when the steps in the episode reach
+ * episode_length; TimeLimit max_steps (truncated = !terminated && steps >= max_steps); NEXT_STEP
+ * autoreset; meta_dev (N, 3) i32 {steps, episodes, pending}, rows and counters as
+ * gs_cartpole_step.  There is no state tensor.
+ * z is a standard normal by Box-Muller, z = sqrt(-2 log(1 - u1)) cos(2 pi u2), with u1, u2 the
+ * 53-bit uniforms of the counter hash of (seed, env_offset + env, episode, step in episode,
+ * component) on tags of its own: it depends on those counters only, so the step loop, a captured
+ * graph and the one-launch rollout draw the same bits.  numpy's PCG64 ziggurat stream is not
+ * reproduced: parity with the reference's own reward stream is unpinned, as for every device env. */
+#define GS_BANDIT_MAX_ARMS 32
+typedef struct gs_bandit_spec {
+    int32_t n_arms, episode_length;            /* 2 .. GS_BANDIT_MAX_ARMS, >= 1 */
+    float means[GS_BANDIT_MAX_ARMS], stds[GS_BANDIT_MAX_ARMS];   /* stds >= 0 */
+} gs_bandit_spec;
+int gs_bandit_reset(int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, gs_bandit_spec spec, int64_t N,
+                    void *stream);
+int gs_bandit_step(int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, gs_bandit_spec spec,
+                   const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed, int64_t env_offset,
+                   float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
+                   int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
+/* gs_rollout_env for the bandit (gs_rollout_env_supported's kind GS_ENV_BANDIT: obs dim ==
+ * n_actions in [2, GS_BANDIT_ROLLOUT_MAX_ARMS] and a policy that fits in LDS; more arms take the
+ * step loop): bit for bit T calls of gs_policy_act + gs_bandit_step.  The bound is the
+ * reference config's 10 arms: the kernel is instantiated for that action count alone. */
+#define GS_BANDIT_ROLLOUT_MAX_ARMS 10
+int gs_rollout_bandit(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
+                      uint64_t rng_counter0, int32_t *env_meta_dev, float *env_ep_ret_dev, float *env_obs_dev,
+                      gs_bandit_spec spec, int32_t max_steps, uint64_t env_seed, int64_t env_offset,
+                      int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, float *obs_rows_dev,
+                      int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev, float *reward_rows_dev,
+                      uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
 
 /* ---------------------------------------------------------------- Acrobot-v1 dynamics (f1)
  * gymnasium 1.x AcrobotEnv.step ("book" variant, no torque noise) restated on device: state
