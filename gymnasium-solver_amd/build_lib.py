@@ -22,7 +22,8 @@ ARCH = "gfx950"
 EXTRA = {"gs_gae.hip": ["-ffp-contract=off"], "gs_mlp.hip": ["-ffp-contract=off"], "gs_atari.hip": ["-ffp-contract=off"],
          "gs_cartpole.hip": ["-ffp-contract=off"], "gs_acrobot.hip": ["-ffp-contract=off"],
          "gs_mountaincar.hip": ["-ffp-contract=off"], "gs_mlp1.hip": ["-ffp-contract=off"],
-         "gs_tabular.hip": ["-ffp-contract=off"], "gs_bandit.hip": ["-ffp-contract=off"]}
+         "gs_tabular.hip": ["-ffp-contract=off"], "gs_bandit.hip": ["-ffp-contract=off"],
+         "gs_mc.hip": ["-ffp-contract=off"]}
 # Kernel-argument preload: the leading 14 dwords of a kernel's plain (non-struct) arguments arrive
 # in SGPRs with the wave, so the update chain's entries (k_fwd_chain / k_bwd_chain, whose argument
 # lists are ordered for it) issue their first load burst without a scalar memory round trip.

@@ -10,7 +10,7 @@ __all__ = ["build_agent", "needs_host_env"]
 
 
 def build_agent(config, *args, **kwargs):
-    """Mirror of agents/__init__.py:1-8 for the device path (algo_id == "ppo")."""
+    """Mirror of agents/__init__.py:1-8 for the device path (algo_id "ppo" or "reinforce")."""
     from .ppo_agent import build_agent as _build
     return _build(config, *args, **kwargs)
 

@@ -28,12 +28,14 @@ METRIC_SLOTS = (
     "explained_var", "kl", "approx_kl", "adv_norm_mean", "adv_norm_std", "kl_stop", "grad_norm",
     "skipped", "unevaluated", "res1",
     # pre-clip per-component gradient norms (utils/models.py:196-230)
+    # slots 20 / 21: GS_M_PG_TARGET_MEAN / _STD in gs_pg_update's records (M["pg_target_mean"], M["pg_target_std"])
     "gn_backbone", "gn_policy_head", "gn_value_head", "gn_mlp", "res20", "res21", "res22", "res23",
     # GS_HP_ACT_STATS: per hooked layer {mean, std, dead_pct, dead_max} (utils/models.py:121-147)
     *(f"act{l}_{k}" for l in range(4) for k in ("mean", "std", "dead_pct", "dead_max")),
 )
 ACT_SLOT = 24                # GS_M_ACT
 M = {name: i for i, name in enumerate(METRIC_SLOTS)}
+M["pg_target_mean"], M["pg_target_std"] = M["res20"], M["res21"]
 
 
 class MlpDims(ctypes.Structure):
@@ -81,6 +83,14 @@ class PPOHparams(ctypes.Structure):
                 ("target_kl", ctypes.c_float), ("normalize_adv", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
+class PGHparams(ctypes.Structure):
+    """gs_pg_hparams (include/gsamd.h): the REINFORCE update's hyper-parameters."""
+    _fields_ = [("ent_coef", ctypes.c_float), ("max_grad_norm", ctypes.c_float), ("lr", ctypes.c_float),
+                ("adam_beta1", ctypes.c_float), ("adam_beta2", ctypes.c_float), ("adam_eps", ctypes.c_float),
+                ("normalize_targets", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+GS_MC_RTG, GS_MC_EPISODE = 0, 1     # include/gsamd.h: gs_mc_returns_f32 kinds
 GS_HP_BF16 = 1      # include/gsamd.h: bf16 MFMA operands in the NatureCNN update
 GS_HP_ACT_STATS = 2  # include/gsamd.h: per-minibatch activation statistics into the records (GS_M_ACT)
 
@@ -126,6 +136,11 @@ def _load():
         "gs_cnn_activation_stats": (ctypes.c_int, [vp, CnnDims, RolloutViewU8, vp, i64, vp, vp, vp]),
         "gs_gae_f32": (ctypes.c_int, [vp, vp, vp, vp, vp, vp, i64, i64, f64, f64, vp, vp, vp]),
         "gs_sampler_stream_i32": (ctypes.c_int, [i64, i64, u64, vp, ctypes.c_int]),
+        "gs_mc_returns_f32": (ctypes.c_int, [vp, vp, vp, i64, i64, f64, ctypes.c_int, vp, vp, vp, vp, vp]),
+        "gs_pg_update_workspace_bytes": (sz, [MlpDims, i64]),
+        "gs_pg_update": (ctypes.c_int, [vp, vp, vp, vp, MlpDims, PGHparams, RolloutView, vp, i64, i64, i64, vp, vp, sz,
+                                        vp, vp]),
+        "gs_pg_loss": (ctypes.c_int, [vp, vp, MlpDims, PGHparams, RolloutView, vp, i64, vp, vp, sz, vp]),
         "gs_mlp_param_count": (i64, [MlpDims]),
         "gs_policy_scratch_bytes": (sz, [MlpDims, i64]),
         "gs_policy_act": (ctypes.c_int, [vp, MlpDims, vp, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
@@ -226,6 +241,7 @@ def _load():
 lib = _load()
 EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_normalize_advantages_scratch_bytes", "gs_normalize_advantages",
             "gs_cnn_activation_stats", "gs_gae_f32", "gs_sampler_stream_i32", "gs_mlp_param_count",
+            "gs_mc_returns_f32", "gs_pg_update_workspace_bytes", "gs_pg_update", "gs_pg_loss",
             "gs_policy_scratch_bytes", "gs_policy_act", "gs_policy_value", "gs_rollout_synth_supported",
             "gs_rollout_synth", "gs_rollout_env_supported", "gs_rollout_env", "gs_env_reset", "gs_env_step",
             "gs_episode_stats", "gs_episode_window",

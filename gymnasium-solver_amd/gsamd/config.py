@@ -196,7 +196,67 @@ class PPOConfig:
                     normalize_advantages=self.normalize_advantages == "rollout")
 
 
+@dataclass
+class REINFORCEConfig(PPOConfig):
+    """The reference's REINFORCEConfig (utils/config.py:806-820) on the device path: Monte Carlo
+    targets, one pass of large minibatches.  Defaults are the reference's; normalize_advantages is a
+    field the reference's class lacks (agents/base_agent.py:117 reads it and raises AttributeError on
+    the first minibatch): here it exists and defaults to "off".  The PPO-only fields (clip ranges,
+    vf_coef, gae_lambda, target_kl) are carried and not read."""
+    algo_id: str = "reinforce"
+    n_steps: int = 2048
+    batch_size: Any = 2048
+    n_epochs: int = 1
+    policy_lr: float = 1e-2
+    gamma: float = 0.99
+    ent_coef: float = 0.01
+    max_grad_norm: float = 0.5
+    normalize_advantages: str = "off"
+    returns_type: str = "mc:rtg"            # "mc:rtg" (reward to go) | "mc:episode" (whole-episode return)
+    policy_targets: str = "returns"         # what the loss scales the log-probabilities by: "returns" | "advantages"
+    normalize_returns: str = "off"          # "off" | "rollout" (the collector) | "batch" (the loss)
+
+    def validate(self):
+        super().validate()
+        for k in ("returns_type", "policy_targets", "normalize_returns"):    # enums of the reference reduce to values
+            setattr(self, k, getattr(getattr(self, k), "value", getattr(self, k)))
+        if self.normalize_returns in (None, False, ""):
+            self.normalize_returns = "off"
+        if self.normalize_advantages in (None, False, ""):
+            self.normalize_advantages = "off"
+        if self.returns_type not in ("mc:rtg", "mc:episode"):
+            raise ValueError(f"returns_type must be 'mc:rtg' or 'mc:episode' for REINFORCE, got {self.returns_type!r}")
+        if self.policy_targets not in ("returns", "advantages"):
+            raise ValueError("policy_targets must be 'returns' or 'advantages'.")
+        if self.normalize_returns not in ("batch", "rollout", "off"):
+            raise ValueError("normalize_returns must be 'rollout', 'batch', or 'off'.")
+        if self.target_kl is not None:
+            raise ValueError("target_kl is a PPO setting: REINFORCE never stops an epoch early")
+
+    def get_rollout_collector_kwargs(self) -> Dict[str, Any]:
+        """utils/config.py:698-718: no advantages_type on this class, so the collector infers "baseline"
+        (utils/rollout_collector.py:57-63)."""
+        return dict(n_steps=self.n_steps, gamma=self.gamma, gae_lambda=self.gae_lambda,
+                    normalize_returns=self.normalize_returns == "rollout", returns_type=self.returns_type,
+                    advantages_type="baseline", normalize_advantages=self.normalize_advantages == "rollout")
+
+
+CONFIG_CLASSES = {"ppo": PPOConfig, "reinforce": REINFORCEConfig}
 _FIELDS = {f.name for f in dataclasses.fields(PPOConfig)}
+_YAML_FIELDS = _FIELDS | {f.name for f in dataclasses.fields(REINFORCEConfig)}
+
+
+def _config_class(algo_id):
+    algo = getattr(algo_id, "value", algo_id) or "ppo"
+    if algo not in CONFIG_CLASSES:
+        raise ValueError(f"device path implements algo_id 'ppo' and 'reinforce' only, got {algo!r}")
+    return CONFIG_CLASSES[algo]
+
+
+def _fields_of(cls):
+    return {f.name for f in dataclasses.fields(cls)}
+
+
 _ALIASES = {"LunarLander-v2": "LunarLander-v3"}
 
 ENV_DYNAMICS = ("auto", "synthetic", "cartpole", "acrobot", "mountaincar", "frozenlake", "taxi", "bandit")
@@ -472,10 +532,10 @@ def _collect_yaml(config_dir: str) -> Dict[str, Dict[str, Any]]:
             doc = yaml.safe_load(f) or {}
         base: Dict[str, Any] = {}
         if isinstance(doc.get("_base"), dict):
-            base.update({k: v for k, v in doc["_base"].items() if k in _FIELDS})
-        base.update({k: v for k, v in doc.items() if k in _FIELDS})
+            base.update({k: v for k, v in doc["_base"].items() if k in _YAML_FIELDS})
+        base.update({k: v for k, v in doc.items() if k in _YAML_FIELDS})
         for k, v in doc.items():
-            if k in _FIELDS or not isinstance(v, dict) or str(k).startswith("_"):
+            if k in _YAML_FIELDS or not isinstance(v, dict) or str(k).startswith("_"):
                 continue
             cfg = dict(base)
             cfg.update(v)
@@ -497,15 +557,21 @@ def load_config(env_id: str, variant: Optional[str] = None, config_dir: Optional
     if config_dir:
         table = _collect_yaml(config_dir)
         raw = dict(table[f"{env_id}_{variant}"])
-        if raw.get("algo_id", "ppo") != "ppo":
-            raise ValueError(f"device path implements algo_id 'ppo' only, got {raw.get('algo_id')}")
     else:
         key = f"{env_id}:{variant}"
         if key not in PRESETS:
             raise KeyError(f"no bundled preset for {key}; pass config_dir=<reference>/config/environments")
         raw = dict(PRESETS[key])
-    raw = {k: v for k, v in raw.items() if k in _FIELDS}
-    cfg = PPOConfig(**raw)
+    cls = _config_class(raw.get("algo_id", "ppo"))
+    raw = {k: v for k, v in raw.items() if k in _fields_of(cls)}
+    if cls is REINFORCEConfig:
+        # upstream defects of Bandit-v0.yaml's reinforce variant: no model_id (the reference asserts at
+        # utils/config.py:463 and cannot start) -> its ppo sibling's mlp_small; n_envs "auto" -> 32
+        if not raw.get("model_id"):
+            raw["model_id"] = "mlp_small"
+        if raw.get("n_envs") in (None, "auto"):
+            raw["n_envs"] = 32
+    cfg = cls(**raw)
     if overrides:
         cfg = apply_overrides(cfg, overrides)
     return cfg
@@ -515,7 +581,7 @@ def apply_overrides(cfg: PPOConfig, overrides: Dict[str, Any]) -> PPOConfig:
     """`--override K=V` (utils/train_launcher.py:81-98): applied after resolution, like the
     reference, but re-validated here (the reference skips re-validation)."""
     for k, v in overrides.items():
-        if k not in _FIELDS:
+        if k not in _fields_of(type(cfg)):
             raise KeyError(f"unknown config field {k!r}")
         cur = getattr(cfg, k)
         if isinstance(v, str) and isinstance(cur, (int, float)) and not isinstance(cur, bool):
@@ -535,7 +601,8 @@ def from_reference_config(cfg: Any, **extras) -> PPOConfig:
         return apply_overrides(cfg, extras) if extras else cfg
     from .schedules import SCHEDULABLE, from_attributes
     kw: Dict[str, Any] = {}
-    for name in _FIELDS:
+    cls = _config_class(getattr(cfg, "algo_id", "ppo"))
+    for name in _fields_of(cls):
         if hasattr(cfg, name) and name != "schedules":
             v = getattr(cfg, name)
             kw[name] = getattr(v, "value", v)
@@ -543,4 +610,7 @@ def from_reference_config(cfg: Any, **extras) -> PPOConfig:
     if sched:
         kw["schedules"] = sched
     kw.update(extras)
-    return PPOConfig(**kw)
+    if cls is REINFORCEConfig:
+        kw = {k: v for k, v in kw.items() if v is not None or k in ("max_epochs", "max_env_steps", "target_kl",
+                                                                    "frame_stack", "max_episode_steps")}
+    return cls(**kw)

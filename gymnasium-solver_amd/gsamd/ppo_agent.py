@@ -3,6 +3,7 @@
 Reference surface mirrored (agents/__init__.py:1-8, agents/base_agent.py:26-885,
 agents/ppo/ppo_agent.py:10-152):
   build_agent(config)                         -> DevicePPOAgent when config.algo_id == "ppo"
+                                                 (DeviceREINFORCEAgent, gsamd/reinforce_agent.py, for "reinforce")
   train_dataloader()                          first rollout + minibatch index stream  (base_agent.py:253-283)
   on_train_epoch_start()                      re-collect from epoch 1 on             (base_agent.py:284-328)
   training_step(batch, batch_idx)             one fused minibatch step               (base_agent.py:330-366)
@@ -834,7 +835,10 @@ def build_agent(config, *args, **kwargs):
     env_dynamics='synthetic'."""
     from .config import from_reference_config
     algo = getattr(getattr(config, "algo_id", None), "value", getattr(config, "algo_id", None))
+    if algo == "reinforce":         # agents/reinforce: Monte Carlo targets + the large-batch policy-gradient update
+        from .reinforce_agent import DeviceREINFORCEAgent
+        return DeviceREINFORCEAgent(from_reference_config(config), *args, **kwargs)
     if algo != "ppo":
-        raise ValueError(f"device path implements algo_id 'ppo' only, got {algo!r}")
+        raise ValueError(f"device path implements algo_id 'ppo' and 'reinforce' only, got {algo!r}")
     return DevicePPOAgent(from_reference_config(config), *args, **kwargs)
 

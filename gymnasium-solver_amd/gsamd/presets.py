@@ -63,6 +63,22 @@ PRESETS = {
         spec={"action_space": {"discrete": 10},
               "observation_space": {"default": "constant_zero",
                                     "variants": {"constant_zero": {"shape": ["n_arms"], "dtype": "float32"}}}}),
+    # Bandit-v0's reinforce variant (config/environments/Bandit-v0.yaml:62-73; record:
+    # tests/golden/config_reinforce.json): REINFORCEConfig's defaults (utils/config.py:806-816) under the
+    # same env.  The yaml names no model_id — the reference asserts at utils/config.py:463 and cannot
+    # start — so this preset takes its ppo sibling's mlp_small (the record keeps null); n_envs "auto"
+    # -> 32, so N T = 32 x 64 = 2048 = batch_size: one optimizer step per rollout.
+    "Bandit-v0:reinforce": dict(
+        algo_id="reinforce", env_id="Bandit-v0", project_id="Bandit-v0", n_envs=32, n_steps=64, batch_size=2048,
+        n_epochs=1, gamma=1.0, gae_lambda=1.0, ent_coef=0.01, max_grad_norm=0.5, policy_lr=0.04, model_id="mlp_small",
+        max_env_steps=20000, obs_type="vector", accelerator="cpu", seed=42, optimizer="adam",
+        returns_type="mc:rtg", policy_targets="returns", normalize_returns="off", normalize_advantages="off",
+        env_kwargs={"n_arms": 10, "means": [0, 1, 2, 3, 4, 5, 6, 7, 8, 9], "stds": 1, "episode_length": 1},
+        schedules={"policy_lr": {"schedule": "linear", "start_value": 0.04, "end_value": 0.0, "start": 0.0,
+                                 "end": 1.0, "warmup": 0.0}},
+        spec={"action_space": {"discrete": 10},
+              "observation_space": {"default": "constant_zero",
+                                    "variants": {"constant_zero": {"shape": ["n_arms"], "dtype": "float32"}}}}),
     "LunarLander-v3:ppo": dict(
         _COMMON, env_id="LunarLander-v3", project_id="LunarLander-v3", n_envs=8, n_steps=2048, batch_size=64,
         n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.0, policy_lr=0.0003,

@@ -484,7 +484,8 @@ class DeviceRolloutCollector:
 
     def __init__(self, env, policy_model, n_steps, *, gamma: float = 0.99, gae_lambda: float = 0.95,
                  stats_window_size: int = 100, rng_seed: int = 42, track_stats: bool = True,
-                 use_graph: bool = True, one_launch: bool = True, normalize_advantages: bool = False, **kwargs):
+                 use_graph: bool = True, one_launch: bool = True, normalize_advantages: bool = False,
+                 returns_type: str = "gae:rtg", advantages_type: str = "gae", normalize_returns: bool = False, **kwargs):
         self.env = env
         self.policy_model = policy_model
         self.n_steps = int(n_steps)
@@ -497,6 +498,17 @@ class DeviceRolloutCollector:
         # utils/rollout_collector.py:441-442 with returns_advantages.py:61-64), after GAE on the device
         self.normalize_advantages = bool(normalize_advantages)
         self._adv_scratch = None
+        # the targets: "gae:rtg" + "gae" (PPO, the default) or the Monte Carlo returns of REINFORCE
+        # ("mc:rtg" / "mc:episode" with advantages_type "baseline"; utils/rollout_collector.py:385-426)
+        self.returns_type, self.advantages_type = str(returns_type), str(advantages_type)
+        if self.returns_type not in ("gae:rtg", "mc:rtg", "mc:episode"):
+            raise ValueError(f"Invalid returns_type: {self.returns_type} and advantages_type: {self.advantages_type}")
+        self.normalize_returns = bool(normalize_returns)
+        # the running baseline over every rollout's valid returns: RunningStats' count / sum /
+        # sum_squared as Python floats (utils/rollout_stats.py:34-67)
+        self._base_stats = {"count": 0, "sum": 0.0, "sum_squared": 0.0}
+        self._mc = None              # device idx_map / last_terminal / valid_sums of the MC targets
+        self.idx_map = None          # this rollout's (N * T) int32 env-major index map on the device, or None
         # device envs: the T-step loop (policy act + env step per vector step) is captured once
         # per sampling mode into a hipGraph and replayed; the per-rollout counters reach the
         # kernels through a 2-word device clock (include/gsamd.h "Rollout clock")
@@ -605,10 +617,13 @@ class DeviceRolloutCollector:
                 self._host_obs = np.asarray(next_obs, dtype=self._host_obs.dtype)
         T = self.n_steps
         last_obs = self.env.obs if native else self._obs_dev.copy_(torch.from_numpy(self._host_obs))
-        pm.predict_values(last_obs, out=buf.last_values)
-        compute_batched_gae_advantages_and_returns(buf.values, buf.rewards, buf.dones, buf.timeouts,
-                                                   buf.last_values, buf.bootstrapped_values, self.gamma,
-                                                   self.gae_lambda, adv_out=buf.advantages, ret_out=buf.returns)
+        if self.returns_type != "gae:rtg":
+            self._compute_mc_targets()          # no value bootstrap, no GAE
+        else:
+            pm.predict_values(last_obs, out=buf.last_values)
+            compute_batched_gae_advantages_and_returns(buf.values, buf.rewards, buf.dones, buf.timeouts,
+                                                       buf.last_values, buf.bootstrapped_values, self.gamma,
+                                                       self.gae_lambda, adv_out=buf.advantages, ret_out=buf.returns)
         self.rollout_steps, self.rollout_vec_steps = N * T, T
         self.total_steps += N * T
         self.total_vec_steps += T
@@ -790,6 +805,55 @@ class DeviceRolloutCollector:
                                  bool(trunc[e]))
         self.rollout_episodes += int(np.count_nonzero(done))
 
+    def baseline_mean(self) -> float:
+        b = self._base_stats
+        return b["sum"] / b["count"] if b["count"] else 0.0
+
+    def _compute_mc_targets(self):
+        """The reference's mc:* branch (utils/rollout_collector.py:385-431) on the device:
+        gs_mc_returns_f32 (returns, the index map up to each env's last terminal, the valid returns'
+        sums; timeouts count as terminals, the reference's mc_treat_timeouts_as_terminals default),
+        the running baseline updated with this rollout's valid returns (one 24-byte read: the
+        baseline is host state, Python floats as RunningStats keeps them), advantages = returns -
+        f32(baseline mean) when advantages_type is "baseline", then the rollout normalisation of the
+        returns (gs_normalize_advantages: its arithmetic is _normalize_returns').  The advantages'
+        rollout normalisation follows in collect(), as for GAE.  The running roll/* statistics cover
+        every position of the rollout (the reference restricts them to the valid ones)."""
+        from ._lib import GS_MC_EPISODE, GS_MC_RTG
+        buf, T, N = self._buffer, self.n_steps, self.n_envs
+        if self._mc is None:
+            self._mc = {"idx_map": torch.zeros(N * T, dtype=torch.int32, device=self.device),
+                        "last_terminal": torch.zeros(N, dtype=torch.int32, device=self.device),
+                        "valid_sums": torch.zeros(3, dtype=torch.float64, device=self.device)}
+        mc = self._mc
+        kind = GS_MC_EPISODE if self.returns_type == "mc:episode" else GS_MC_RTG
+        check(lib.gs_mc_returns_f32(ptr(buf.rewards), ptr(buf.dones), None, T, N, float(self.gamma), kind,
+                                    ptr(buf.returns), ptr(mc["idx_map"]), ptr(mc["last_terminal"]),
+                                    ptr(mc["valid_sums"]), stream_handle()), "gs_mc_returns_f32")
+        count, total, squares = mc["valid_sums"].cpu().tolist()
+        if count > 0:
+            b = self._base_stats
+            b["count"] += int(count)
+            b["sum"] += float(total)
+            b["sum_squared"] += float(squares)
+            self.idx_map = mc["idx_map"]
+        else:
+            self.idx_map = None          # nothing valid: the reference keeps no map
+        if self.advantages_type == "baseline":
+            torch.sub(buf.returns, float(np.float32(self.baseline_mean())), out=buf.advantages)
+        else:
+            buf.advantages.copy_(buf.returns)
+        if self.normalize_returns:
+            self._normalize_in_place(buf.returns)
+
+    def _normalize_in_place(self, x, mean_std=None):
+        if self._adv_scratch is None:
+            nb = int(lib.gs_normalize_advantages_scratch_bytes(x.numel()))
+            self._adv_scratch = torch.zeros(max(1, nb // 4), dtype=torch.float32, device=self.device)
+            self.adv_mean_std = torch.zeros(2, dtype=torch.float32, device=self.device)
+        check(lib.gs_normalize_advantages(ptr(x), x.numel(), 1e-8, ptr(self._adv_scratch), ptr(mean_std),
+                                          stream_handle()), "gs_normalize_advantages")
+
     def _normalize_rollout_advantages(self):
         """adv = (adv - mean) / (std + 1e-8) over the whole rollout in place
         (gs_normalize_advantages; utils/returns_advantages.py:61-64), after the pre-normalisation
@@ -885,6 +949,8 @@ class DeviceRolloutCollector:
     def slice_trajectories(self, trajectories, idxs):
         """utils/rollout_collector.py:657-682 — index the env-major views."""
         idx = torch.as_tensor(idxs, dtype=torch.int64, device=self.device)
+        if self.idx_map is not None:        # MC targets: every index -> its nearest earlier valid position
+            idx = self.idx_map.long()[idx]
         from types import SimpleNamespace
         return SimpleNamespace(**{f: getattr(trajectories, f)[idx] for f in DeviceTrajectory._FIELDS[:-1]})
 
@@ -944,7 +1010,8 @@ class DeviceRolloutCollector:
             m["action_dist"] = hist
         else:
             m["roll/actions/mean"], m["roll/actions/std"], m["action_dist"] = 0.0, 0.0, None
-        m["roll/baseline/mean"], m["roll/baseline/std"] = zero
+        b = self._base_stats             # the MC baseline (GAE targets never update it: zeros)
+        m["roll/baseline/mean"], m["roll/baseline/std"] = mean_std(b["sum"], b["sum_squared"], b["count"])
         if self.normalize_advantages and n_stats and s[12] > 0:      # rollout_collector.py:748-750
             m["roll/adv_norm/mean"], m["roll/adv_norm/std"] = mean_std(s[10], s[11], s[12])
         if dev_eps:

@@ -267,6 +267,9 @@ enum gs_metric_slot {
      * value_head, and the NatureCNN mlp (fc) trunk (0 for the MLP policy) */
     GS_M_GN_BACKBONE, GS_M_GN_POLICY_HEAD, GS_M_GN_VALUE_HEAD, GS_M_GN_MLP,
     GS_M_RES20, GS_M_RES21, GS_M_RES22, GS_M_RES23,
+    /* gs_pg_update / gs_pg_loss (REINFORCE): mean and unbiased std of the policy targets the loss
+     * used (after the batch normalisation, when on) — the reserved slots 20 / 21 by another name */
+    GS_M_PG_TARGET_MEAN = GS_M_RES20, GS_M_PG_TARGET_STD = GS_M_RES21,
     /* GS_HP_ACT_STATS: 4 layers x {mean, std, dead_pct, dead_max} of the pre-activation outputs */
     GS_M_ACT = 24
 };
@@ -399,6 +402,69 @@ int gs_ppo_global_adv_stats(const int32_t *idx_dev, int64_t n_minibatches, int64
                             float *adv_stats_dev, void *stream);
 int gs_ppo_global_records(const gs_ppo_hparams *hp, int64_t n_minibatches, int64_t batch_global, struct gs_comm *comm,
                           double *metric_sums_dev, float *metrics_dev, void *stream);
+
+/* ---------------------------------------------------------------- REINFORCE (Monte Carlo returns + policy-gradient update)
+ * The reference's second algorithm (agents/reinforce/reinforce_agent.py:11-88 on the targets of
+ * utils/rollout_collector.py:385-457).
+ *
+ * gs_mc_returns_f32 replaces compute_batched_mc_returns (utils/returns_advantages.py:67-91),
+ * convert_returns_to_full_episode (:93-113, kind GS_MC_EPISODE) and _build_valid_mask_and_index_map
+ * (:33-52) on time-major (T, N) rows.  timeouts_dev NULL: every done cuts the return (the
+ * reference's mc_treat_timeouts_as_terminals=True default); non-NULL: a terminal is done && !timeout.
+ * returns_dev (T, N): bit-exact with the reference's float32 loop acc = r + f32(gamma) * (acc * nt),
+ * three roundings, no FMA.  last_terminal_dev (N): each env's last terminal step, -1 = none; an
+ * env's positions 0 .. last terminal are valid.  idx_map_dev (N * T int32, env-major i = env * T + t;
+ * may be NULL): every position's nearest earlier-or-equal valid position, positions before the first
+ * valid one map to it; with nothing valid the identity (the reference keeps no map then).
+ * valid_sums_dev (3 doubles): {count, sum, sum of squares} of the valid returns, summed in double
+ * in a fixed order (per env in step order, then over envs).  Two launches, no host round trip.
+ * T * N < 2^31. */
+#define GS_MC_RTG 0
+#define GS_MC_EPISODE 1
+int gs_mc_returns_f32(const float *rewards_dev, const uint8_t *dones_dev, const uint8_t *timeouts_dev, int64_t T,
+                      int64_t N, double gamma, int kind, float *returns_dev, int32_t *idx_map_dev,
+                      int32_t *last_terminal_dev, double *valid_sums_dev, void *stream);
+
+/* REINFORCEAgent.losses_for_batch + BaseAgent._backpropagate_and_step on minibatches of up to 2^20
+ * rows (the reference's batch_size is 2048, beyond the PPO entries' 1024): per optimizer step one
+ * row-parallel launch (forward, loss, backward; workgroups own 16-row tiles and add their gradient
+ * share into their own partial slot) and one step launch (the slots summed in workgroup order, the
+ * norms, clip_grad_norm_, Adam).
+ *   loss = -mean(logp * t) - ent_coef * mean(entropy),  t = rollout.advantages[row], normalised over
+ *   the minibatch as (t - mean) / (std_unbiased + 1e-8) when normalize_targets != 0.
+ * rollout.advantages carries the policy targets (returns or advantages, as the caller chose);
+ * rollout.values / .returns are not read and may be NULL.  The value head is outside the loss: its
+ * gradient is None in the reference, so clip_grad_norm_ and Adam skip it — its slice of params,
+ * adam_m and adam_v is not written at all, its slice of grads is zeros.  Every reduction has a
+ * fixed order (no float atomics): two runs give the same bytes.
+ * Record per minibatch (GS_NUM_METRICS floats): LOSS, POLICY_LOSS, ENTROPY, KL, APPROX_KL,
+ * ADV_NORM_MEAN / _STD (the normalised targets' mean / unbiased std when normalising, else 0),
+ * GRAD_NORM, GN_BACKBONE, GN_POLICY_HEAD, GS_M_PG_TARGET_MEAN / _STD; every other slot 0.
+ * Shapes: obs_dim in [1, 64], hidden1 / hidden2 in [1, 512], n_actions in [1, 32]; batch in
+ * [2, 2^20]; idx_dev: n_minibatches * batch env-major sample indices.  GS_E_INVALID for hidden2 == 0
+ * (one hidden layer), GS_HP_BF16 in flags and a non-NULL communicator.  workspace_dev: 16-byte
+ * aligned, gs_pg_update_workspace_bytes(dims, batch) bytes — it grows with min(row tiles, 256), not
+ * with batch (one parameter-sized slot per row workgroup: at 4096 rows or more 18 MB for 4-128-128-2,
+ * 69 MB for 4-256-256-2).  gs_pg_loss: the same forward, loss and gradient (into grads_dev) and the record,
+ * no optimizer step. */
+typedef struct gs_pg_hparams {
+    float ent_coef;
+    float max_grad_norm;        /* <= 0: no clipping */
+    float lr;
+    float adam_beta1;
+    float adam_beta2;
+    float adam_eps;
+    int32_t normalize_targets;  /* 1 = "batch" (utils/torch.py:97-99), 0 = off */
+    int32_t flags;              /* GS_HP_BF16 is refused; other bits ignored */
+} gs_pg_hparams;
+size_t gs_pg_update_workspace_bytes(gs_mlp_dims dims, int64_t batch);
+int gs_pg_update(float *params_dev, float *grads_dev, float *adam_m_dev, float *adam_v_dev, gs_mlp_dims dims,
+                 gs_pg_hparams hp, gs_rollout_view rollout, const int32_t *idx_dev, int64_t batch,
+                 int64_t n_minibatches, int64_t adam_step0, float *metrics_dev, void *workspace_dev,
+                 size_t workspace_bytes, struct gs_comm *comm, void *stream);
+int gs_pg_loss(const float *params_dev, float *grads_dev, gs_mlp_dims dims, gs_pg_hparams hp, gs_rollout_view rollout,
+               const int32_t *idx_dev, int64_t batch, float *metrics_dev, void *workspace_dev, size_t workspace_bytes,
+               void *stream);
 
 /* ---------------------------------------------------------------- NatureCNN actor-critic (C4/C5)
  * Replaces CNNActorCritic (utils/models.py:347-455; conv 8x8s4 -> 4x4s2 -> 3x3s1 with 32/64/64
