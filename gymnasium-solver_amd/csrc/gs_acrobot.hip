@@ -2,78 +2,26 @@
 //
 // The reference trains `Acrobot-v1:ppo` on gymnasium 1.x's AcrobotEnv (not vendored: gymnasium is
 // absent offline, so parity with its trajectories is UNPINNED, exactly as for CartPole).  The
-// published dynamics are restated in gs_acrobot_env.h (the per-env arithmetic, shared with the
-// one-launch rollout): "book" equations, one RK4 step of dt = 0.2 in double precision, bounded
+// published dynamics are restated in gs_acrobot_env.h (the env type, shared with the
+// one-launch rollout; the kernels are gs_env_kernels.h's): "book" equations, one RK4 step of dt = 0.2 in double precision, bounded
 // angle wraps, velocity clamps, termination above the line, reward -1 (0 on the terminating
 // step), TimeLimit truncation at 500 steps, and the vector env's NEXT_STEP autoreset: the step
 // after a done resets that env, ignores its action and returns the reset observation with
 // reward 0 and no done flag.  Reset states are uniform in [-0.1, 0.1) from a counter-based hash,
 // rounded to float32 (numpy's PCG64 stream is not reproduced).  The numpy twin is
 // tests/acrobot_twin.py.
-#include <math.h>
-
-#include "gs_common.h"
+#include "gs_env_kernels.h"
 #include "gs_acrobot_env.h"
 
-namespace {
-
 using namespace gs;
-
-__global__ __launch_bounds__(256) void k_acrobot_reset(double *__restrict__ st, int32_t *__restrict__ meta,
-                                                       float *__restrict__ ep_ret, float *__restrict__ obs, int64_t N,
-                                                       uint64_t seed, int64_t env_offset)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= N) return;
-    ACState s;
-    acrobot_reset_state(s, seed, (uint64_t)(env_offset + e), 0);
-    reinterpret_cast<ACState *>(st)[e] = s;
-    meta[3 * e + 0] = 0;   // steps in the current episode
-    meta[3 * e + 1] = 0;   // episodes finished (the reset counter)
-    meta[3 * e + 2] = 0;   // 1 = the previous step ended an episode (autoreset pending)
-    ep_ret[e] = 0.0f;
-    acrobot_write_obs(s, obs + 6 * e);
-}
-
-__global__ __launch_bounds__(256) void k_acrobot_step(double *__restrict__ st, int32_t *__restrict__ meta,
-                                                      float *__restrict__ ep_ret, float *__restrict__ obs,
-                                                      const int64_t *__restrict__ actions, int64_t N, int max_steps,
-                                                      uint64_t seed, int64_t env_offset, float *__restrict__ rew_row,
-                                                      uint8_t *__restrict__ done_row, uint8_t *__restrict__ to_row,
-                                                      int32_t *__restrict__ ep_cnt, float *__restrict__ ep_ret_sum,
-                                                      float *__restrict__ ep_len_sum)
-{
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e >= N) return;
-    ACState s = reinterpret_cast<ACState *>(st)[e];
-    int32_t m[3] = {meta[3 * e + 0], meta[3 * e + 1], meta[3 * e + 2]};
-    float er = ep_ret[e];
-    const EnvStepOut so = acrobot_env_step(s, m, er, actions[e], max_steps, seed, (uint64_t)(env_offset + e),
-                                           ep_cnt ? ep_cnt + e : nullptr, ep_ret_sum ? ep_ret_sum + e : nullptr,
-                                           ep_len_sum ? ep_len_sum + e : nullptr);
-    rew_row[e] = so.reward;
-    done_row[e] = so.done ? 1 : 0;
-    to_row[e] = so.timeout ? 1 : 0;
-    meta[3 * e + 0] = m[0];
-    meta[3 * e + 1] = m[1];
-    meta[3 * e + 2] = m[2];
-    ep_ret[e] = er;
-    reinterpret_cast<ACState *>(st)[e] = s;
-    acrobot_write_obs(s, obs + 6 * e);
-}
-
-inline unsigned nblk(int64_t n) { return (unsigned)((n + 255) / 256); }
-
-}  // namespace
 
 extern "C" int gs_acrobot_reset(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev, int64_t N,
                                 uint64_t seed, int64_t env_offset, void *stream)
 {
     GS_REQUIRE(N > 0 && state_dev && meta_dev && ep_ret_dev && obs_dev, "gs_acrobot_reset: bad argument");
-    hipLaunchKernelGGL(k_acrobot_reset, dim3(nblk(N)), dim3(256), 0, (hipStream_t)stream, state_dev, meta_dev,
-                       ep_ret_dev, obs_dev, N, seed, env_offset);
-    GS_LAUNCH_CHECK("k_acrobot_reset");
-    return GS_OK;
+    const AcrobotEnv::Args ev{{meta_dev, ep_ret_dev, obs_dev, nullptr, nullptr, nullptr, 0, seed, env_offset},
+                              state_dev};
+    return launch_env_reset<AcrobotEnv>(ev, N, stream);
 }
 
 extern "C" int gs_acrobot_step(double *state_dev, int32_t *meta_dev, float *ep_ret_dev, float *obs_dev,
@@ -85,9 +33,8 @@ extern "C" int gs_acrobot_step(double *state_dev, int32_t *meta_dev, float *ep_r
     GS_REQUIRE(N > 0 && state_dev && meta_dev && ep_ret_dev && obs_dev && actions_dev && max_steps > 0,
                "gs_acrobot_step: bad argument");
     GS_REQUIRE(rewards_row_dev && dones_row_dev && timeouts_row_dev, "gs_acrobot_step: null output row");
-    hipLaunchKernelGGL(k_acrobot_step, dim3(nblk(N)), dim3(256), 0, (hipStream_t)stream, state_dev, meta_dev,
-                       ep_ret_dev, obs_dev, actions_dev, N, max_steps, seed, env_offset, rewards_row_dev,
-                       dones_row_dev, timeouts_row_dev, ep_done_count_dev, ep_ret_sum_dev, ep_len_sum_dev);
-    GS_LAUNCH_CHECK("k_acrobot_step");
-    return GS_OK;
+    const AcrobotEnv::Args ev{{meta_dev, ep_ret_dev, obs_dev, ep_done_count_dev, ep_ret_sum_dev, ep_len_sum_dev,
+                               max_steps, seed, env_offset},
+                              state_dev};
+    return launch_env_step<AcrobotEnv>(ev, actions_dev, N, rewards_row_dev, dones_row_dev, timeouts_row_dev, stream);
 }

@@ -1,6 +1,6 @@
-// gs_acrobot_env.h — device Acrobot-v1's per-env arithmetic, shared by its step kernels
-// (gs_acrobot.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), so both produce the
-// same bits.  Both files compile with -ffp-contract=off.  Twin: tests/acrobot_twin.py.
+// gs_acrobot_env.h — device Acrobot-v1: the env type AcrobotEnv behind its step kernels
+// (gs_acrobot.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), see gs_env_episode.h.
+// Twin: tests/acrobot_twin.py.
 //
 // gymnasium is not vendored and not installed, so the dynamics are restated from the published
 // gymnasium 1.x AcrobotEnv ("book" variant, no torque noise) and parity with gymnasium's own
@@ -11,7 +11,7 @@
 // counter hash, rounded to float32 (gymnasium's reset casts its state to float32).
 #pragma once
 
-#include "gs_cartpole_env.h"   // env_reset_unit, EnvStepOut
+#include "gs_env_episode.h"
 
 namespace gs {
 
@@ -89,19 +89,9 @@ __device__ __forceinline__ double acrobot_clamp(double x, double lim)
     return x < -lim ? -lim : (x > lim ? lim : x);
 }
 
-// One env's step: state, meta {steps, episodes, pending} and the running return advance; on a
-// done the (null-tolerant) episode counters add the finished episode.  ge = the global env index.
-__device__ __forceinline__ EnvStepOut acrobot_env_step(ACState &s, int32_t (&meta)[3], float &er, int64_t action,
-                                                       int max_steps, uint64_t seed, uint64_t ge, int32_t *ep_cnt,
-                                                       float *ep_ret_sum, float *ep_len_sum)
+// AcrobotEnv.step: one RK4 step, wrap and clamp; returns terminated
+__device__ __forceinline__ bool acrobot_dynamics(ACState &s, int64_t action)
 {
-    if (meta[2] != 0) {        // NEXT_STEP autoreset: this step only resets
-        acrobot_reset_state(s, seed, ge, (uint64_t)meta[1]);
-        meta[0] = 0;
-        meta[2] = 0;
-        er = 0.0f;
-        return EnvStepOut{0.0f, false, false};
-    }
     const double a = (double)(action - 1);
     // classical RK4, y' = y + dt/6 (k1 + 2 k2 + 2 k3 + k4); the stages share one copy of the
     // derivative's code (stage 0 reads y + 0 * 0 = y)
@@ -120,20 +110,17 @@ __device__ __forceinline__ EnvStepOut acrobot_env_step(ACState &s, int32_t (&met
     s.t2 = acrobot_wrap(s.t2 + kAcDt / 6.0 * acc.t2);
     s.w1 = acrobot_clamp(s.w1 + kAcDt / 6.0 * acc.w1, kAcMaxVel1);
     s.w2 = acrobot_clamp(s.w2 + kAcDt / 6.0 * acc.w2, kAcMaxVel2);
-    const bool terminated = -cos(s.t1) - cos(s.t1 + s.t2) > 1.0;
-    const float reward = terminated ? 0.0f : -1.0f;
-    const int steps = meta[0] + 1;
-    const bool truncated = !terminated && steps >= max_steps;
-    er = er + reward;
-    if (terminated || truncated) {
-        if (ep_cnt) *ep_cnt += 1;
-        if (ep_ret_sum) *ep_ret_sum += er;
-        if (ep_len_sum) *ep_len_sum += (float)steps;
-        meta[1] += 1;
-        meta[2] = 1;
-    }
-    meta[0] = steps;
-    return EnvStepOut{reward, terminated || truncated, truncated};
+    return -cos(s.t1) - cos(s.t1 + s.t2) > 1.0;
 }
+
+struct AcrobotEnv : DynEnv<ACState, 6, 3, acrobot_reset_state, acrobot_write_obs> {
+    using Args = DynEnvArgs;
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        if (reset_row(ev, me)) return EnvStepOut{};
+        const bool terminated = acrobot_dynamics(s, action);
+        return finish_step(ev, me, terminated ? 0.0f : -1.0f, terminated);
+    }
+};
 
 }  // namespace gs

@@ -1,6 +1,6 @@
-// gs_bandit_env.h — device Bandit-v0's per-env arithmetic, shared by the step kernels
-// (gs_bandit.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), so both produce the same
-// bits.  Both files compile with -ffp-contract=off.  Twin: tests/bandit_twin.py.
+// gs_bandit_env.h — device Bandit-v0: the env type BanditEnv behind the step kernels
+// (gs_bandit.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), see gs_env_episode.h.
+// Twin: tests/bandit_twin.py.
 //
 // The env restates the reference's gym_envs/mab_env.py MultiArmedBanditEnv: a stateless Gaussian
 // multi-armed bandit whose observation is zeros(n_arms), reward = mean[a] + std[a] z in double
@@ -17,8 +17,7 @@
 // 0xC0 + c of env_reset_unit.
 #pragma once
 
-#include "gs_cartpole_env.h"   // env_mix64, EnvStepOut
-#include "../../include/gsamd.h"
+#include "gs_env_episode.h"
 
 namespace gs {
 
@@ -37,36 +36,43 @@ __device__ __forceinline__ double bandit_normal(uint64_t seed, uint64_t env, uin
     return sqrt(-2.0 * log(1.0 - u1)) * cos(2.0 * M_PI * u2);
 }
 
-// One env's step: meta {steps, episodes, pending} and the running return advance; on a done the
-// (null-tolerant) episode counters add the finished episode.  ge = the global env index.  An
-// action outside [0, n_arms) is clamped, so no index leaves the spec's arrays.
-__device__ __forceinline__ EnvStepOut bandit_env_step(int32_t (&meta)[3], float &er, int64_t action, int max_steps,
-                                                      uint64_t seed, uint64_t ge, const gs_bandit_spec &sp,
-                                                      int32_t *ep_cnt, float *ep_ret_sum, float *ep_len_sum)
-{
-    if (meta[2] != 0) {        // NEXT_STEP autoreset: this step only resets
-        meta[0] = 0;
-        meta[2] = 0;
-        er = 0.0f;
-        return EnvStepOut{0.0f, false, false};
+// null, or what is wrong with the spec: every bandit entry checks this before a launch, so no
+// index leaves the spec's arrays (gs_bandit.hip)
+const char *bandit_spec_error(const gs_bandit_spec &sp);
+
+// No state beyond meta and the running return; the observation rows stay zero.  An action outside
+// [0, n_arms) is clamped, so no index leaves the spec's arrays.  The policy of a one-launch rollout
+// has n_arms actions: a 10-action runtime shape serves the reference's 10 arms (head_act_row's sums
+// run over a < A in order, so its rows equal gs_policy_act's 32-action shape); more arms take the
+// step loop.
+struct BanditEnv : EnvEpisode {
+    struct Args : EnvArgs {
+        gs_bandit_spec sp;
+    };
+    static constexpr int kRolloutAmax = GS_BANDIT_ROLLOUT_MAX_ARMS;
+    static bool takes_policy(int D, int A) { return D == A && A >= 2 && A <= GS_BANDIT_ROLLOUT_MAX_ARMS; }
+    static __device__ __forceinline__ int obs_dim(const Args &ev) { return ev.sp.n_arms; }
+    __device__ __forceinline__ void load(const Args &ev, int64_t me) { load_episode(ev, me); }
+    __device__ __forceinline__ void store(const Args &ev, int64_t me) const { store_episode(ev, me); }
+    __device__ __forceinline__ void reset(const Args &, int64_t) { reset_episode(); }
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        if (autoreset()) return EnvStepOut{};
+        const gs_bandit_spec &sp = ev.sp;
+        const int last = (sp.n_arms < GS_BANDIT_MAX_ARMS ? sp.n_arms : GS_BANDIT_MAX_ARMS) - 1;
+        const int a = action < 0 ? 0 : (action > last ? last : (int)action);
+        const double z = bandit_normal(ev.seed, (uint64_t)(ev.env_offset + me), (uint64_t)meta[1], (uint64_t)meta[0]);
+        const float reward = (float)((double)sp.means[a] + (double)sp.stds[a] * z);
+        return finish_step(ev, me, reward, meta[0] + 1 >= sp.episode_length);
     }
-    const int last = (sp.n_arms < GS_BANDIT_MAX_ARMS ? sp.n_arms : GS_BANDIT_MAX_ARMS) - 1;
-    const int a = action < 0 ? 0 : (action > last ? last : (int)action);
-    const double z = bandit_normal(seed, ge, (uint64_t)meta[1], (uint64_t)meta[0]);
-    const float reward = (float)((double)sp.means[a] + (double)sp.stds[a] * z);
-    const int steps = meta[0] + 1;
-    const bool terminated = steps >= sp.episode_length;
-    const bool truncated = !terminated && steps >= max_steps;
-    er = er + reward;
-    if (terminated || truncated) {
-        if (ep_cnt) *ep_cnt += 1;
-        if (ep_ret_sum) *ep_ret_sum += er;
-        if (ep_len_sum) *ep_len_sum += (float)steps;
-        meta[1] += 1;
-        meta[2] = 1;
+    __device__ __forceinline__ void write_obs(const Args &ev, float *o) const
+    {
+        for (int d = 0; d < ev.sp.n_arms; ++d) o[d] = 0.0f;
     }
-    meta[0] = steps;
-    return EnvStepOut{reward, terminated || truncated, truncated};
-}
+    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int D, int, int tid, bool) const
+    {
+        for (int u = tid; u < 16 * D; u += 256) xs[u] = 0.0f;
+    }
+};
 
 }  // namespace gs

@@ -1,38 +1,12 @@
-// gs_cartpole_env.h — device CartPole-v1's per-env arithmetic, shared by its step kernels
-// (gs_cartpole.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), so both produce the
-// same bits.  Both files compile with -ffp-contract=off.  Twin: oracle/cartpole_ref.py.
-// Also the pieces every device env with real dynamics shares: the counter hash of the reset
-// draws and the step's result.  At the end: the reference's CartPoleV1_RewardShaper on top of the
-// same step (cartpole_phi, cartpole_shaped_env_step; twin tests/cartpole_shaper_twin.py).
+// gs_cartpole_env.h — device CartPole-v1: the env type CartPoleEnv behind its step kernels
+// (gs_cartpole.hip) and the one-launch rollout (gs_mlp.hip k_rollout_env), see gs_env_episode.h.
+// Twin: oracle/cartpole_ref.py.  At the end: the reference's CartPoleV1_RewardShaper on top of the
+// same dynamics (cartpole_phi, CartPoleShapedEnv; twin tests/cartpole_shaper_twin.py).
 #pragma once
 
-#include <math.h>
-#include <stdint.h>
-
-#include "../../include/gsamd.h"   // gs_cartpole_wrappers
+#include "gs_env_episode.h"
 
 namespace gs {
-
-__device__ __forceinline__ uint64_t env_mix64(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
-// uniform in [0, 1): 53-bit mantissa from the hash of (seed, env, episode, component)
-__device__ __forceinline__ double env_reset_unit(uint64_t seed, uint64_t env, uint64_t episode, int c)
-{
-    const uint64_t h = env_mix64(env_mix64(env_mix64(env_mix64(seed) ^ env) ^ episode) ^ (uint64_t)(0xC0 + c));
-    return (double)(h >> 11) * (1.0 / 9007199254740992.0);
-}
-
-// what one env step writes into the rollout rows
-struct EnvStepOut {
-    float reward;
-    bool done, timeout;
-};
 
 struct CPState {      // per env, double precision like gymnasium's Python-float state
     double x, x_dot, theta, theta_dot;
@@ -60,20 +34,9 @@ __device__ __forceinline__ void cartpole_write_obs(const CPState &s, float *o)
     o[3] = (float)s.theta_dot;
 }
 
-// One env's step: state, meta {steps, episodes, pending} and the running return advance; on a
-// done the (null-tolerant) episode counters add the finished episode.  ge = the global env index.
-__device__ __forceinline__ EnvStepOut cartpole_env_step(CPState &s, int32_t (&meta)[3], float &er, int64_t action,
-                                                        int max_steps, uint64_t seed, uint64_t ge, int32_t *ep_cnt,
-                                                        float *ep_ret_sum, float *ep_len_sum)
+// gymnasium CartPoleEnv.step (euler): the state advances; returns terminated
+__device__ __forceinline__ bool cartpole_dynamics(CPState &s, int64_t action)
 {
-    if (meta[2] != 0) {        // NEXT_STEP autoreset: this step only resets
-        cartpole_reset_state(s, seed, ge, (uint64_t)meta[1]);
-        meta[0] = 0;
-        meta[2] = 0;
-        er = 0.0f;
-        return EnvStepOut{0.0f, false, false};
-    }
-    // gymnasium CartPoleEnv.step (euler)
     const double gravity = 9.8, masscart = 1.0, masspole = 0.1, total_mass = masspole + masscart;
     const double length = 0.5, polemass_length = masspole * length, force_mag = 10.0, tau = 0.02;
     const double theta_threshold = 12.0 * 2.0 * M_PI / 360.0, x_threshold = 2.4;
@@ -87,21 +50,18 @@ __device__ __forceinline__ EnvStepOut cartpole_env_step(CPState &s, int32_t (&me
     s.x_dot = s.x_dot + tau * xacc;
     s.theta = s.theta + tau * s.theta_dot;
     s.theta_dot = s.theta_dot + tau * thetaacc;
-    const bool terminated = s.x < -x_threshold || s.x > x_threshold || s.theta < -theta_threshold ||
-                            s.theta > theta_threshold;
-    const int steps = meta[0] + 1;
-    const bool truncated = !terminated && steps >= max_steps;
-    er = er + 1.0f;
-    if (terminated || truncated) {
-        if (ep_cnt) *ep_cnt += 1;
-        if (ep_ret_sum) *ep_ret_sum += er;
-        if (ep_len_sum) *ep_len_sum += (float)steps;
-        meta[1] += 1;
-        meta[2] = 1;
-    }
-    meta[0] = steps;
-    return EnvStepOut{1.0f, terminated || truncated, truncated};
+    return s.x < -x_threshold || s.x > x_threshold || s.theta < -theta_threshold || s.theta > theta_threshold;
 }
+
+struct CartPoleEnv : DynEnv<CPState, 4, 2, cartpole_reset_state, cartpole_write_obs> {
+    using Args = DynEnvArgs;
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        if (reset_row(ev, me)) return EnvStepOut{};
+        const bool terminated = cartpole_dynamics(s, action);
+        return finish_step(ev, me, 1.0f, terminated);
+    }
+};
 
 // CartPoleV1_RewardShaper._phi (the reference's gym_wrappers/CartPoleV1/reward_shaper.py) on the
 // float32 observation's x and theta, in double as the class's float(obs[i]) arithmetic; the
@@ -125,34 +85,44 @@ __device__ __forceinline__ double cartpole_phi(const gs_cartpole_wrappers &w, co
     return cartpole_phi(w, (float)s.x, (float)s.theta);
 }
 
-// One env's step under the shaper: cartpole_env_step's dynamics, flags, meta and reset hash, with
-// reward = (float)(1.0 + (phi - prev_phi)) and the running return adding that reward.  The
-// wrapper's reset() takes the reset observation's potential, so a NEXT_STEP autoreset row stays
-// reward 0 and re-arms prev_phi.
-__device__ __forceinline__ EnvStepOut cartpole_shaped_env_step(CPState &s, double &prev_phi, int32_t (&meta)[3],
-                                                               float &er, int64_t action, int max_steps,
-                                                               uint64_t seed, uint64_t ge,
-                                                               const gs_cartpole_wrappers &w, int32_t *ep_cnt,
-                                                               float *ep_ret_sum, float *ep_len_sum)
-{
-    const bool reset_row = meta[2] != 0;
-    float unshaped = 0.0f;     // the dynamics' own return accumulator is not this env's
-    const EnvStepOut so = cartpole_env_step(s, meta, unshaped, action, max_steps, seed, ge, nullptr, nullptr, nullptr);
-    const double phi = cartpole_phi(w, s);
-    if (reset_row) {
+// The env under the shaper: CartPoleEnv's dynamics, flags, meta and reset hash, with reward =
+// (float)(1.0 + (phi - prev_phi)) and the running return adding that reward.  The wrapper's
+// reset() takes the reset observation's potential, so a NEXT_STEP autoreset row stays reward 0
+// and re-arms prev_phi.  The previous potentials are an (N) f64 tensor of their own; thread `me`
+// keeps its env's in a register.
+struct CartPoleShapedEnv : CartPoleEnv {
+    struct Args : DynEnvArgs {
+        double *prev_phi;
+        gs_cartpole_wrappers w;
+    };
+    double prev_phi;
+    __device__ __forceinline__ void load(const Args &ev, int64_t me)
+    {
+        CartPoleEnv::load(ev, me);
+        prev_phi = ev.prev_phi[me];
+    }
+    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
+    {
+        CartPoleEnv::store(ev, me);
+        ev.prev_phi[me] = prev_phi;
+    }
+    __device__ __forceinline__ void reset(const Args &ev, int64_t me)
+    {
+        CartPoleEnv::reset(ev, me);
+        prev_phi = cartpole_phi(ev.w, s);
+    }
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        if (reset_row(ev, me)) {
+            prev_phi = cartpole_phi(ev.w, s);
+            return EnvStepOut{};
+        }
+        const bool terminated = cartpole_dynamics(s, action);
+        const double phi = cartpole_phi(ev.w, s);
+        const float reward = (float)(1.0 + (phi - prev_phi));
         prev_phi = phi;
-        er = 0.0f;
-        return so;
+        return finish_step(ev, me, reward, terminated);
     }
-    const float reward = (float)(1.0 + (phi - prev_phi));
-    prev_phi = phi;
-    er = er + reward;
-    if (so.done) {
-        if (ep_cnt) *ep_cnt += 1;
-        if (ep_ret_sum) *ep_ret_sum += er;
-        if (ep_len_sum) *ep_len_sum += (float)meta[0];
-    }
-    return EnvStepOut{reward, so.done, so.timeout};
-}
+};
 
 }  // namespace gs

@@ -292,61 +292,16 @@ struct RolloutRows {                 // time-major (T, N) rows of the rollout bu
     uint8_t *done, *timeout;
 };
 
-// One-launch rollout of a device env with real dynamics (gs_mlp.hip k_rollout_env; the kinds
-// are include/gsamd.h's GS_ENV_CARTPOLE / GS_ENV_ACROBOT, obs dims 4 / 6, 2 / 3 actions)
-struct DynEnvArgs {
-    double *state;                   // [N][4]
-    int32_t *meta;                   // [N][3] {steps, episodes, pending}
-    float *ep_ret, *obs;             // [N], [N][D]
-    int32_t *ep_cnt;                 // [N] finished-episode counters (may be null)
-    float *ep_ret_sum, *ep_len_sum;
-    int max_steps;
-    uint64_t seed;
-    int64_t env_offset;
-};
-// MountainCar (GS_ENV_MOUNTAINCAR, obs dim 2, 3 actions): the same tensors plus the count tables
-// [N][position_bins * velocity_bins] (HBM; null without a count bonus) and the wrappers
-struct MountainCarEnvArgs : DynEnvArgs {
-    int32_t *counts;
-    gs_mountaincar_wrappers w;
-};
-
 bool rollout_synth_fits(const Layout &L);
 int launch_rollout_synth(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
                          uint64_t counter0, const SynthEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
+// One-launch rollout of a device env with real dynamics (gs_mlp.hip k_rollout_env<S, E>): E is the
+// env type of a gs_*_env.h header, instantiated in gs_mlp.hip for CartPoleEnv, CartPoleShapedEnv,
+// AcrobotEnv, MountainCarEnv and BanditEnv; the kinds are include/gsamd.h's GS_ENV_*
 bool rollout_env_fits(const Layout &L, int kind);
-int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                       uint64_t counter0, int kind, const DynEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
-// null, or what is wrong with the wrappers (their order, the bonus' table and parameters): every
-// MountainCar entry checks this before a launch, so no index leaves an env's table (gs_mountaincar.hip)
-const char *mountaincar_wrappers_error(const gs_mountaincar_wrappers &w, const void *counts);
-int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                               uint64_t counter0, const MountainCarEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
-// CartPole under the reference's reward shaper (kind GS_ENV_CARTPOLE's shape): the same tensors
-// plus the wrapper's previous potential [N] and its parameters
-struct CartPoleShapedEnvArgs : DynEnvArgs {
-    double *prev_phi;
-    gs_cartpole_wrappers w;
-};
-int launch_rollout_cartpole_shaped(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                                   uint64_t counter0, const CartPoleShapedEnvArgs &ev, const RolloutRows &rw,
-                                   hipStream_t s);
-// Bandit-v0 (GS_ENV_BANDIT, obs dim == actions == n_arms): no state tensor
-struct BanditEnvArgs {
-    int32_t *meta;                   // [N][3] {steps, episodes, pending}
-    float *ep_ret, *obs;             // [N], [N][n_arms] (zeros)
-    int32_t *ep_cnt;                 // [N] finished-episode counters (may be null)
-    float *ep_ret_sum, *ep_len_sum;
-    int max_steps;
-    uint64_t seed;
-    int64_t env_offset;
-    gs_bandit_spec sp;
-};
-// null, or what is wrong with the spec: every bandit entry checks this before a launch, so no
-// index leaves the spec's arrays (gs_bandit.hip)
-const char *bandit_spec_error(const gs_bandit_spec &sp);
-int launch_rollout_bandit(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                          uint64_t counter0, const BanditEnvArgs &ev, const RolloutRows &rw, hipStream_t s);
+template <class E>
+int launch_rollout(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed, uint64_t counter0,
+                   const typename E::Args &ev, const RolloutRows &rw, hipStream_t s);
 
 inline int n_col_blocks(int H) { return (H + kTile - 1) / kTile; }
 inline int n_sumsq_slots(const Layout &L) { return n_col_blocks(L.H2) * n_col_blocks(L.H1) + 2 * n_col_blocks(L.H2) + 1; }

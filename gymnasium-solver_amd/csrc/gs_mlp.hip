@@ -1091,8 +1091,9 @@ __global__ __launch_bounds__(256) void k_heads_act(const float *__restrict__ P, 
 
 // ------------------------------------------------------------------------------------
 // k_rollout_env: a whole rollout of a device env in one launch (C3-sized MLPs, whose
-// weights fit in LDS), generic over the env E: the synthetic env, CartPole, Acrobot or MountainCar.  Workgroup = 16 envs (one MFMA row tile) for all T vector steps: the
-// policy's act with gs_policy_act's arithmetic in its order (h1 fmaf chain + bias; each h2
+// weights fit in LDS), generic over the env E: the synthetic env below or an env type of a
+// gs_*_env.h header (gs_env_episode.h lists what E provides).  Workgroup = 16 envs (one MFMA row
+// tile) for all T vector steps: the policy's act with gs_policy_act's arithmetic in its order (h1 fmaf chain + bias; each h2
 // column block's 4 K-range MFMA partials summed in range order, as the 4 waves of
 // k_fwd_hidden do; partial heads per column block summed in block order as k_heads_act), so the
 // rows are bit-identical to the step-wise rollout; then the env step (E::step, the arithmetic of
@@ -1138,139 +1139,6 @@ struct RolloutSynthEnv {
         ev.state[4 * me + 0] = st[0];
         ev.state[4 * me + 1] = st[1];
         ev.state[4 * me + 2] = st[2];
-        ev.ep_ret[me] = er;
-    }
-};
-
-// CartPole / Acrobot: State, its step and its observation come from the env's header
-template <class State, int OBS_DIM>
-struct RolloutDynEnvBase {
-    using Args = DynEnvArgs;
-    State s;
-    int32_t meta[3];
-    float er;
-    __device__ __forceinline__ void load(const Args &ev, int64_t me)
-    {
-        s = reinterpret_cast<const State *>(ev.state)[me];
-        meta[0] = ev.meta[3 * me + 0];
-        meta[1] = ev.meta[3 * me + 1];
-        meta[2] = ev.meta[3 * me + 2];
-        er = ev.ep_ret[me];
-    }
-    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
-    {
-        reinterpret_cast<State *>(ev.state)[me] = s;
-        ev.meta[3 * me + 0] = meta[0];
-        ev.meta[3 * me + 1] = meta[1];
-        ev.meta[3 * me + 2] = meta[2];
-        ev.ep_ret[me] = er;
-    }
-};
-struct RolloutCartPoleEnv : RolloutDynEnvBase<CPState, 4> {
-    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
-    {
-        return cartpole_env_step(s, meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me),
-                                 ev.ep_cnt ? ev.ep_cnt + me : nullptr, ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
-                                 ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
-    }
-    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
-                                             bool env_thread) const
-    {
-        if (env_thread) cartpole_write_obs(s, xs + 4 * tid);
-    }
-};
-struct RolloutAcrobotEnv : RolloutDynEnvBase<ACState, 6> {
-    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
-    {
-        return acrobot_env_step(s, meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me),
-                                ev.ep_cnt ? ev.ep_cnt + me : nullptr, ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
-                                ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
-    }
-    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
-                                             bool env_thread) const
-    {
-        if (env_thread) acrobot_write_obs(s, xs + 6 * tid);
-    }
-};
-
-// MountainCar: its own Args (the count tables and the wrappers ride behind DynEnvArgs), so the
-// other instantiations' kernel arguments stay where they are.  The tables stay in HBM: thread
-// `me` reads and bumps one cell of env me's table per step.
-struct RolloutMountainCarEnv : RolloutDynEnvBase<MCState, 2> {
-    using Args = MountainCarEnvArgs;
-    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
-    {
-        int32_t *table = ev.counts ? ev.counts + me * ((int64_t)ev.w.position_bins * ev.w.velocity_bins) : nullptr;
-        return mountaincar_env_step(s, meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me), ev.w,
-                                    table, ev.ep_cnt ? ev.ep_cnt + me : nullptr,
-                                    ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
-                                    ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
-    }
-    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
-                                             bool env_thread) const
-    {
-        if (env_thread) mountaincar_write_obs(s, xs + 2 * tid);
-    }
-};
-
-// CartPole under the reference's reward shaper: its own Args (the previous potentials and the
-// wrapper's parameters ride behind DynEnvArgs); thread `me` keeps its env's previous potential in a
-// register for the whole launch.
-struct RolloutCartPoleShapedEnv : RolloutDynEnvBase<CPState, 4> {
-    using Args = CartPoleShapedEnvArgs;
-    using Base = RolloutDynEnvBase<CPState, 4>;
-    double prev_phi;
-    __device__ __forceinline__ void load(const Args &ev, int64_t me)
-    {
-        Base::load(ev, me);
-        prev_phi = ev.prev_phi[me];
-    }
-    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
-    {
-        return cartpole_shaped_env_step(s, prev_phi, meta, er, action, ev.max_steps, ev.seed,
-                                        (uint64_t)(ev.env_offset + me), ev.w, ev.ep_cnt ? ev.ep_cnt + me : nullptr,
-                                        ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
-                                        ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
-    }
-    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int, int, int tid,
-                                             bool env_thread) const
-    {
-        if (env_thread) cartpole_write_obs(s, xs + 4 * tid);
-    }
-    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
-    {
-        Base::store(ev, me);
-        ev.prev_phi[me] = prev_phi;
-    }
-};
-
-// Bandit-v0: no state beyond meta and the running return; the observation rows stay zero
-struct RolloutBanditEnv {
-    using Args = BanditEnvArgs;
-    int32_t meta[3];
-    float er;
-    __device__ __forceinline__ void load(const Args &ev, int64_t me)
-    {
-        meta[0] = ev.meta[3 * me + 0];
-        meta[1] = ev.meta[3 * me + 1];
-        meta[2] = ev.meta[3 * me + 2];
-        er = ev.ep_ret[me];
-    }
-    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
-    {
-        return bandit_env_step(meta, er, action, ev.max_steps, ev.seed, (uint64_t)(ev.env_offset + me), ev.sp,
-                               ev.ep_cnt ? ev.ep_cnt + me : nullptr, ev.ep_ret_sum ? ev.ep_ret_sum + me : nullptr,
-                               ev.ep_len_sum ? ev.ep_len_sum + me : nullptr);
-    }
-    __device__ __forceinline__ void next_obs(const Args &, float *xs, int64_t, int64_t, int D, int, int tid, bool) const
-    {
-        for (int u = tid; u < kTile * D; u += 256) xs[u] = 0.0f;
-    }
-    __device__ __forceinline__ void store(const Args &ev, int64_t me) const
-    {
-        ev.meta[3 * me + 0] = meta[0];
-        ev.meta[3 * me + 1] = meta[1];
-        ev.meta[3 * me + 2] = meta[2];
         ev.ep_ret[me] = er;
     }
 };
@@ -1488,56 +1356,40 @@ int launch_rollout_synth(const float *P, const Layout &L, int64_t N, int T, int 
 }
 
 // the env kinds of include/gsamd.h with real dynamics: the policy's shape must be the env's
+template <class E>
+static bool rollout_fits(const Layout &L)
+{
+    return E::takes_policy(L.D, L.A) && rollout_synth_fits(L);
+}
+
 bool rollout_env_fits(const Layout &L, int kind)
 {
-    if (kind == GS_ENV_CARTPOLE) return L.D == 4 && L.A == 2 && rollout_synth_fits(L);
-    if (kind == GS_ENV_ACROBOT) return L.D == 6 && L.A == 3 && rollout_synth_fits(L);
-    if (kind == GS_ENV_MOUNTAINCAR) return L.D == 2 && L.A == 3 && rollout_synth_fits(L);
-    if (kind == GS_ENV_BANDIT)
-        return L.D == L.A && L.A >= 2 && L.A <= GS_BANDIT_ROLLOUT_MAX_ARMS && rollout_synth_fits(L);
+    if (kind == GS_ENV_CARTPOLE) return rollout_fits<CartPoleEnv>(L);
+    if (kind == GS_ENV_ACROBOT) return rollout_fits<AcrobotEnv>(L);
+    if (kind == GS_ENV_MOUNTAINCAR) return rollout_fits<MountainCarEnv>(L);
+    if (kind == GS_ENV_BANDIT) return rollout_fits<BanditEnv>(L);
     return false;
 }
 
-// Neither env's dims are a compile-time shape of with_shape that fits in LDS (CartPole's
-// 4-256-256-2 does not fit), so both run on the runtime shape gs_policy_act takes for them.
-int launch_rollout_env(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                       uint64_t counter0, int kind, const DynEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
+// The envs run on the runtime shape gs_policy_act takes for their dims (E::kRolloutAmax).
+template <class E>
+int launch_rollout(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed, uint64_t counter0,
+                   const typename E::Args &ev, const RolloutRows &rw, hipStream_t s)
 {
-    GS_REQUIRE(rollout_env_fits(L, kind), "gs_rollout_env: env kind %d does not take this policy in one launch", kind);
-    if (kind == GS_ENV_CARTPOLE)
-        return launch_rollout_sh<ShapeR<4>, RolloutCartPoleEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
-    return launch_rollout_sh<ShapeR<4>, RolloutAcrobotEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
+    GS_REQUIRE(rollout_fits<E>(L),
+               "one-launch rollout: the policy (obs dim %d, %d actions) is not the env's or does not fit in LDS", L.D,
+               L.A);
+    return launch_rollout_sh<ShapeR<E::kRolloutAmax>, E>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
 }
-
-int launch_rollout_mountaincar(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                               uint64_t counter0, const MountainCarEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
-{
-    GS_REQUIRE(rollout_env_fits(L, GS_ENV_MOUNTAINCAR),
-               "gs_rollout_mountaincar: the policy is not MountainCar's (obs dim 2, 3 actions) or does not fit in LDS");
-    return launch_rollout_sh<ShapeR<4>, RolloutMountainCarEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
-}
-
-int launch_rollout_cartpole_shaped(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                                   uint64_t counter0, const CartPoleShapedEnvArgs &ev, const RolloutRows &rw,
-                                   hipStream_t s)
-{
-    GS_REQUIRE(rollout_env_fits(L, GS_ENV_CARTPOLE),
-               "gs_rollout_cartpole_shaped: the policy is not CartPole's (obs dim 4, 2 actions) or does not fit in LDS");
-    return launch_rollout_sh<ShapeR<4>, RolloutCartPoleShapedEnv>(P, L, N, T, mode, rng_seed, counter0, ev, rw, s);
-}
-
-// The bandit's policy has n_arms actions: a 10-action runtime shape serves the reference's 10 arms
-// (head_act_row's sums run over a < A in order, so its rows equal gs_policy_act's 32-action shape);
-// more arms take the step loop
-int launch_rollout_bandit(const float *P, const Layout &L, int64_t N, int T, int mode, uint64_t rng_seed,
-                          uint64_t counter0, const BanditEnvArgs &ev, const RolloutRows &rw, hipStream_t s)
-{
-    GS_REQUIRE(rollout_env_fits(L, GS_ENV_BANDIT) && L.A == ev.sp.n_arms,
-               "gs_rollout_bandit: the policy is not the bandit's (obs dim = actions = n_arms <= %d) or does not fit "
-               "in LDS", GS_BANDIT_ROLLOUT_MAX_ARMS);
-    return launch_rollout_sh<ShapeR<GS_BANDIT_ROLLOUT_MAX_ARMS>, RolloutBanditEnv>(P, L, N, T, mode, rng_seed,
-                                                                                    counter0, ev, rw, s);
-}
+#define GS_ROLLOUT_INSTANCE(E)                                                                                  \
+    template int launch_rollout<E>(const float *, const Layout &, int64_t, int, int, uint64_t, uint64_t,       \
+                                   const E::Args &, const RolloutRows &, hipStream_t)
+GS_ROLLOUT_INSTANCE(CartPoleEnv);
+GS_ROLLOUT_INSTANCE(CartPoleShapedEnv);
+GS_ROLLOUT_INSTANCE(AcrobotEnv);
+GS_ROLLOUT_INSTANCE(MountainCarEnv);
+GS_ROLLOUT_INSTANCE(BanditEnv);
+#undef GS_ROLLOUT_INSTANCE
 
 // ------------------------------------------------------------------------------------
 // k_loss: single workgroup of 256 threads over the B <= 1024 minibatch rows.

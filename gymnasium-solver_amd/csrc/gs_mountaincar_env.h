@@ -1,7 +1,6 @@
-// gs_mountaincar_env.h — device MountainCar-v0's per-env arithmetic and its two reward wrappers,
-// shared by the step kernels (gs_mountaincar.hip) and the one-launch rollout (gs_mlp.hip
-// k_rollout_env), so both produce the same bits.  Both files compile with -ffp-contract=off.
-// Twin: tests/mountaincar_twin.py.
+// gs_mountaincar_env.h — device MountainCar-v0 and its two reward wrappers: the env type
+// MountainCarEnv behind the step kernels (gs_mountaincar.hip) and the one-launch rollout
+// (gs_mlp.hip k_rollout_env), see gs_env_episode.h.  Twin: tests/mountaincar_twin.py.
 //
 // gymnasium is not vendored and not installed, so the dynamics are restated from the published
 // gymnasium 1.x MountainCarEnv and parity with gymnasium's own episodes is UNPINNED, exactly as
@@ -17,8 +16,7 @@
 // float64), in the config's list order (first entry innermost, its addend first).
 #pragma once
 
-#include "gs_cartpole_env.h"   // env_reset_unit, EnvStepOut
-#include "../../include/gsamd.h"
+#include "gs_env_episode.h"
 
 namespace gs {
 
@@ -79,53 +77,43 @@ __device__ __forceinline__ double mountaincar_bonus(const gs_mountaincar_wrapper
     return w.bonus_scale * bonus;
 }
 
-// One env's step: state, meta {steps, episodes, pending} and the running return advance; on a
-// done the (null-tolerant) episode counters add the finished episode.  ge = the global env
-// index, table = this env's count table (only read with a count bonus in w.order).
-__device__ __forceinline__ EnvStepOut mountaincar_env_step(MCState &s, int32_t (&meta)[3], float &er, int64_t action,
-                                                           int max_steps, uint64_t seed, uint64_t ge,
-                                                           const gs_mountaincar_wrappers &w, int32_t *table,
-                                                           int32_t *ep_cnt, float *ep_ret_sum, float *ep_len_sum)
-{
-    if (meta[2] != 0) {        // NEXT_STEP autoreset: this step only resets; no wrapper adds anything
-        mountaincar_reset_state(s, seed, ge, (uint64_t)meta[1]);
-        meta[0] = 0;
-        meta[2] = 0;
-        er = 0.0f;
-        return EnvStepOut{0.0f, false, false};
-    }
-    // gymnasium MountainCarEnv.step
-    double v = s.v + ((double)(action - 1) * kMcForce + cos(3.0 * s.p) * (-kMcGravity));
-    v = v < -kMcMaxV ? -kMcMaxV : (v > kMcMaxV ? kMcMaxV : v);
-    double p = s.p + v;
-    p = p < kMcMinP ? kMcMinP : (p > kMcMaxP ? kMcMaxP : p);
-    if (p == kMcMinP && v < 0.0) v = 0.0;
-    s.p = p;
-    s.v = v;
-    const bool terminated = p >= kMcGoalP && v >= kMcGoalV;
-    // the wrappers, innermost first, on the float32 observation
-    const double po = (double)(float)p, vo = (double)(float)v;
-    double r = -1.0;
+// null, or what is wrong with the wrappers (their order, the bonus' table and parameters): every
+// MountainCar entry checks this before a launch, so no index leaves an env's table (gs_mountaincar.hip)
+const char *mountaincar_wrappers_error(const gs_mountaincar_wrappers &w, const void *counts);
+
+// The count tables are int32 [N][position_bins * velocity_bins] in HBM (null without a count
+// bonus): thread `me` reads and bumps one cell of local env me's table per step.
+struct MountainCarEnv : DynEnv<MCState, 2, 3, mountaincar_reset_state, mountaincar_write_obs> {
+    struct Args : DynEnvArgs {
+        int32_t *counts;
+        gs_mountaincar_wrappers w;
+    };
+    __device__ __forceinline__ EnvStepOut step(const Args &ev, int64_t me, int64_t action)
+    {
+        if (reset_row(ev, me)) return EnvStepOut{};        // no wrapper adds anything to the reset row
+        const gs_mountaincar_wrappers &w = ev.w;
+        int32_t *table = ev.counts ? ev.counts + me * ((int64_t)w.position_bins * w.velocity_bins) : nullptr;
+        // gymnasium MountainCarEnv.step
+        double v = s.v + ((double)(action - 1) * kMcForce + cos(3.0 * s.p) * (-kMcGravity));
+        v = v < -kMcMaxV ? -kMcMaxV : (v > kMcMaxV ? kMcMaxV : v);
+        double p = s.p + v;
+        p = p < kMcMinP ? kMcMinP : (p > kMcMaxP ? kMcMaxP : p);
+        if (p == kMcMinP && v < 0.0) v = 0.0;
+        s.p = p;
+        s.v = v;
+        const bool terminated = p >= kMcGoalP && v >= kMcGoalV;
+        // the wrappers, innermost first, on the float32 observation
+        const double po = (double)(float)p, vo = (double)(float)v;
+        double r = -1.0;
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        if (w.order[i] == GS_MC_WRAP_SHAPER) r = r + mountaincar_shaping(w, po, vo, s.prev_p, s.prev_v);
-        else if (w.order[i] == GS_MC_WRAP_BONUS) r = r + mountaincar_bonus(w, table, po, vo);
+        for (int i = 0; i < 2; ++i) {
+            if (w.order[i] == GS_MC_WRAP_SHAPER) r = r + mountaincar_shaping(w, po, vo, s.prev_p, s.prev_v);
+            else if (w.order[i] == GS_MC_WRAP_BONUS) r = r + mountaincar_bonus(w, table, po, vo);
+        }
+        s.prev_p = po;
+        s.prev_v = vo;
+        return finish_step(ev, me, (float)r, terminated);
     }
-    s.prev_p = po;
-    s.prev_v = vo;
-    const float reward = (float)r;
-    const int steps = meta[0] + 1;
-    const bool truncated = !terminated && steps >= max_steps;
-    er = er + reward;
-    if (terminated || truncated) {
-        if (ep_cnt) *ep_cnt += 1;
-        if (ep_ret_sum) *ep_ret_sum += er;
-        if (ep_len_sum) *ep_len_sum += (float)steps;
-        meta[1] += 1;
-        meta[2] = 1;
-    }
-    meta[0] = steps;
-    return EnvStepOut{reward, terminated || truncated, truncated};
-}
+};
 
 }  // namespace gs

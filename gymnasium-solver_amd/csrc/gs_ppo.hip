@@ -14,6 +14,10 @@
 #include <vector>
 
 #include "gs_comm_internal.h"
+#include "gs_cartpole_env.h"
+#include "gs_acrobot_env.h"
+#include "gs_mountaincar_env.h"
+#include "gs_bandit_env.h"
 
 namespace gs {
 
@@ -182,6 +186,39 @@ extern "C" int gs_rollout_env_supported(gs_mlp_dims dims, int kind, int *support
     return GS_OK;
 }
 
+// What the one-launch rollout entries of the envs with real dynamics check alike, under the
+// entry's name: the policy's dims, N / T, mode, max_steps and the buffers every env has (an entry
+// checks its own tensors and parameters itself).
+static int check_rollout_entry(const char *who, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                               const float *params, const EnvArgs &ev, const RolloutRows &rw)
+{
+    GS_REQUIRE(!one_layer(dims), "%s: not available for a policy with one hidden layer (hidden2 == 0)", who);
+    int rc = check_dims(dims);
+    if (rc) return rc;
+    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "%s: bad N / T", who);
+    GS_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d not in {0,1,2}", who, mode);
+    GS_REQUIRE(ev.max_steps > 0, "%s: max_steps must be > 0", who);
+    GS_REQUIRE(params && ev.meta && ev.ep_ret && ev.obs && rw.obs && rw.actions && rw.logp && rw.value &&
+                   rw.reward && rw.done && rw.timeout,
+               "%s: null buffer", who);
+    return GS_OK;
+}
+
+// the rollout of env type E behind its entry: the shared checks, then `bad` (null, or what the
+// entry found wrong with its own tensors and parameters); nothing to do for T == 0
+template <class E>
+static int rollout_entry(const char *who, const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                         uint64_t rng_seed, uint64_t rng_counter0, const typename E::Args &ev, const RolloutRows &rw,
+                         const char *bad, void *stream)
+{
+    int rc = check_rollout_entry(who, dims, N, T, mode, params, ev, rw);
+    if (rc) return rc;
+    GS_REQUIRE(!bad, "%s: %s", who, bad);
+    if (T == 0) return GS_OK;
+    return launch_rollout<E>(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
+                             (hipStream_t)stream);
+}
+
 extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
                               uint64_t rng_counter0, int kind, double *env_state, int32_t *env_meta,
                               float *env_ep_ret, float *env_obs, int32_t max_steps, uint64_t env_seed,
@@ -189,26 +226,18 @@ extern "C" int gs_rollout_env(const float *params, gs_mlp_dims dims, int64_t N, 
                               float *obs_rows, int64_t *action_rows, float *logp_rows, float *value_rows,
                               float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows, void *stream)
 {
-    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_env");
-    int rc = check_dims(dims);
-    if (rc) return rc;
-    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_env: bad N / T");
-    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_env: mode %d not in {0,1,2}", mode);
     GS_REQUIRE(kind != GS_ENV_MOUNTAINCAR,
                "gs_rollout_env: MountainCar takes its count tables and wrappers through gs_rollout_mountaincar");
     GS_REQUIRE(kind != GS_ENV_BANDIT, "gs_rollout_env: the bandit takes its spec through gs_rollout_bandit");
     GS_REQUIRE(kind == GS_ENV_CARTPOLE || kind == GS_ENV_ACROBOT,
                "gs_rollout_env: env kind %d has no dynamics here (the synthetic env: gs_rollout_synth)", kind);
-    GS_REQUIRE(max_steps > 0, "gs_rollout_env: max_steps must be > 0");
-    GS_REQUIRE(params && env_state && env_meta && env_ep_ret && env_obs && obs_rows && action_rows && logp_rows &&
-                   value_rows && reward_rows && done_rows && timeout_rows,
-               "gs_rollout_env: null buffer");
-    if (T == 0) return GS_OK;
-    DynEnvArgs ev{env_state, env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
-                  env_seed, env_offset};
-    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
-    return launch_rollout_env(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, kind, ev, rw,
-                              (hipStream_t)stream);
+    const DynEnvArgs ev{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps, env_seed,
+                         env_offset},
+                        env_state};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    const auto run = kind == GS_ENV_CARTPOLE ? rollout_entry<CartPoleEnv> : rollout_entry<AcrobotEnv>;
+    return run("gs_rollout_env", params, dims, N, T, mode, rng_seed, rng_counter0, ev, rw,
+               env_state ? nullptr : "null buffer", stream);
 }
 
 extern "C" int gs_rollout_mountaincar(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
@@ -220,24 +249,15 @@ extern "C" int gs_rollout_mountaincar(const float *params, gs_mlp_dims dims, int
                                       float *value_rows, float *reward_rows, uint8_t *done_rows,
                                       uint8_t *timeout_rows, void *stream)
 {
-    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_mountaincar");
-    int rc = check_dims(dims);
-    if (rc) return rc;
-    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_mountaincar: bad N / T");
-    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_mountaincar: mode %d not in {0,1,2}", mode);
-    GS_REQUIRE(max_steps > 0, "gs_rollout_mountaincar: max_steps must be > 0");
-    GS_REQUIRE(params && env_state && env_meta && env_ep_ret && env_obs && obs_rows && action_rows && logp_rows &&
-                   value_rows && reward_rows && done_rows && timeout_rows,
-               "gs_rollout_mountaincar: null buffer");
-    const char *bad = mountaincar_wrappers_error(wrappers, env_counts);
-    GS_REQUIRE(!bad, "gs_rollout_mountaincar: %s", bad);
-    if (T == 0) return GS_OK;
-    MountainCarEnvArgs ev{{env_state, env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
-                           env_seed, env_offset},
-                          env_counts, wrappers};
-    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
-    return launch_rollout_mountaincar(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
-                                      (hipStream_t)stream);
+    const MountainCarEnv::Args ev{{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
+                                    env_seed, env_offset},
+                                   env_state},
+                                  env_counts,
+                                  wrappers};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    const char *bad = env_state ? mountaincar_wrappers_error(wrappers, env_counts) : "null buffer";
+    return rollout_entry<MountainCarEnv>("gs_rollout_mountaincar", params, dims, N, T, mode, rng_seed, rng_counter0,
+                                         ev, rw, bad, stream);
 }
 
 extern "C" int gs_rollout_cartpole_shaped(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
@@ -249,22 +269,15 @@ extern "C" int gs_rollout_cartpole_shaped(const float *params, gs_mlp_dims dims,
                                           float *value_rows, float *reward_rows, uint8_t *done_rows,
                                           uint8_t *timeout_rows, void *stream)
 {
-    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_cartpole_shaped");
-    int rc = check_dims(dims);
-    if (rc) return rc;
-    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_cartpole_shaped: bad N / T");
-    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_cartpole_shaped: mode %d not in {0,1,2}", mode);
-    GS_REQUIRE(max_steps > 0, "gs_rollout_cartpole_shaped: max_steps must be > 0");
-    GS_REQUIRE(params && env_state && env_prev_phi && env_meta && env_ep_ret && env_obs && obs_rows && action_rows &&
-                   logp_rows && value_rows && reward_rows && done_rows && timeout_rows,
-               "gs_rollout_cartpole_shaped: null buffer");
-    if (T == 0) return GS_OK;
-    CartPoleShapedEnvArgs ev{{env_state, env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum,
-                              max_steps, env_seed, env_offset},
-                             env_prev_phi, wrappers};
-    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
-    return launch_rollout_cartpole_shaped(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
-                                          (hipStream_t)stream);
+    const CartPoleShapedEnv::Args ev{{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum,
+                                       max_steps, env_seed, env_offset},
+                                      env_state},
+                                     env_prev_phi,
+                                     wrappers};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return rollout_entry<CartPoleShapedEnv>("gs_rollout_cartpole_shaped", params, dims, N, T, mode, rng_seed,
+                                            rng_counter0, ev, rw,
+                                            env_state && env_prev_phi ? nullptr : "null buffer", stream);
 }
 
 extern "C" int gs_rollout_bandit(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
@@ -274,23 +287,14 @@ extern "C" int gs_rollout_bandit(const float *params, gs_mlp_dims dims, int64_t 
                                  float *obs_rows, int64_t *action_rows, float *logp_rows, float *value_rows,
                                  float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows, void *stream)
 {
-    GS_REFUSE_ONE_LAYER(dims, "gs_rollout_bandit");
-    int rc = check_dims(dims);
-    if (rc) return rc;
-    GS_REQUIRE(N > 0 && T >= 0 && T < (int64_t)1 << 31, "gs_rollout_bandit: bad N / T");
-    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_rollout_bandit: mode %d not in {0,1,2}", mode);
-    GS_REQUIRE(max_steps > 0, "gs_rollout_bandit: max_steps must be > 0");
-    GS_REQUIRE(params && env_meta && env_ep_ret && env_obs && obs_rows && action_rows && logp_rows && value_rows &&
-                   reward_rows && done_rows && timeout_rows,
-               "gs_rollout_bandit: null buffer");
+    const BanditEnv::Args ev{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
+                              env_seed, env_offset},
+                             spec};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
     const char *bad = bandit_spec_error(spec);
-    GS_REQUIRE(!bad, "gs_rollout_bandit: %s", bad);
-    if (T == 0) return GS_OK;
-    BanditEnvArgs ev{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps, env_seed,
-                     env_offset, spec};
-    RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
-    return launch_rollout_bandit(params, layout_of(dims), N, (int)T, mode, rng_seed, rng_counter0, ev, rw,
-                                 (hipStream_t)stream);
+    if (!bad && T > 0 && dims.n_actions != spec.n_arms) bad = "the policy's actions are not the spec's n_arms";
+    return rollout_entry<BanditEnv>("gs_rollout_bandit", params, dims, N, T, mode, rng_seed, rng_counter0, ev, rw,
+                                    bad, stream);
 }
 
 extern "C" int gs_policy_value(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, float *value,

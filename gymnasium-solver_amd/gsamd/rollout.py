@@ -38,25 +38,51 @@ from .distributed import allreduce_sum_f64
 from .rollout_stats import RollingWindow
 
 
-class DeviceSyntheticVecEnv:
-    """Device twin of gsamd.synthetic_env.SyntheticVecEnv (same hash, same episodes)."""
+class DeviceVecEnv:
+    """What the device env classes share: the tensors every env kernel takes (meta, the running
+    return, the observation, the three finished-episode counters) and the argument groups of the
+    one-launch rollout entries.  An env class adds its own tensors and parameters, reset(),
+    step_into() and, where its kernels have one, rollout_into(): its one-launch rollout call."""
 
     device_native = True
 
-    def __init__(self, n_envs, obs_dim, n_actions, episode_len=200, seed=42, truncate_every=0, env_offset=0,
-                 reward=1.0, device="cuda"):
+    def _alloc(self, n_envs, obs_dim, n_actions, seed, env_offset, device, meta=True):
         self.num_envs, self.obs_dim, self.n_actions = int(n_envs), int(obs_dim), int(n_actions)
-        self.episode_len, self.seed, self.truncate_every = int(episode_len), int(seed), int(truncate_every)
-        self.env_offset, self.reward = int(env_offset), float(reward)
+        self.seed, self.env_offset = int(seed), int(env_offset)
         self.obs_shape, self.obs_dtype = (self.obs_dim,), torch.float32
         self.device = torch.device(device)
-        N = self.num_envs
-        self.state = torch.zeros(4 * N, dtype=torch.int32, device=self.device)
-        self.ep_ret = torch.zeros(N, dtype=torch.float32, device=self.device)
-        self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, device=self.device)
-        self.ep_count = torch.zeros(N, dtype=torch.int32, device=self.device)
-        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, device=self.device)
-        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, device=self.device)
+        N, z = self.num_envs, dict(device=self.device)
+        if meta:
+            self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
+        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
+        self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, **z)
+        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
+        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
+        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
+        return N, z
+
+    def _episode_counters(self):
+        return ptr(self.ep_count), ptr(self.ep_ret_sum), ptr(self.ep_len_sum)
+
+    def _policy_args(self, pm, buf, mode, rng_seed, counter0):
+        """The leading arguments of every gs_rollout_* entry."""
+        return ptr(pm.params), pm.dims, self.num_envs, buf.T, int(mode), int(rng_seed), int(counter0)
+
+    @staticmethod
+    def _row_args(buf):
+        """The trailing arguments of every gs_rollout_* entry: the buffer's rows and the stream."""
+        return (ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values), ptr(buf.rewards),
+                ptr(buf.dones), ptr(buf.timeouts), stream_handle())
+
+
+class DeviceSyntheticVecEnv(DeviceVecEnv):
+    """Device twin of gsamd.synthetic_env.SyntheticVecEnv (same hash, same episodes)."""
+
+    def __init__(self, n_envs, obs_dim, n_actions, episode_len=200, seed=42, truncate_every=0, env_offset=0,
+                 reward=1.0, device="cuda"):
+        N, z = self._alloc(n_envs, obs_dim, n_actions, seed, env_offset, device, meta=False)
+        self.episode_len, self.truncate_every, self.reward = int(episode_len), int(truncate_every), float(reward)
+        self.state = torch.zeros(4 * N, dtype=torch.int32, **z)
         self.step_count = 0
 
     def reset(self):
@@ -73,16 +99,23 @@ class DeviceSyntheticVecEnv:
         check(lib.gs_env_step(ptr(self.state), ptr(self.ep_ret), ptr(self.obs), self.num_envs, self.obs_dim,
                               self.episode_len, self.truncate_every, self.reward, self.seed, self.env_offset,
                               self.step_count if clock is None else int(step), ptr(rewards_row), ptr(dones_row),
-                              ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum), ptr(self.ep_len_sum),
-                              ptr(clock), stream_handle()), "gs_env_step")
+                              ptr(timeouts_row), *self._episode_counters(), ptr(clock), stream_handle()),
+              "gs_env_step")
+
+    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
+        """gs_rollout_synth, after which the host step counter advances by the rollout's T."""
+        check(lib.gs_rollout_synth(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
+                                   ptr(self.ep_ret), ptr(self.obs), self.episode_len, self.truncate_every,
+                                   self.reward, self.seed, self.env_offset, self.step_count,
+                                   *self._episode_counters(), *self._row_args(buf)), "gs_rollout_synth")
+        self.step_count += buf.T
 
 
-class DeviceCartPoleVecEnv:
+class DeviceCartPoleVecEnv(DeviceVecEnv):
     """CartPole-v1 on device (gymnasium 1.x dynamics restated in
     csrc/gs_cartpole.hip, NEXT_STEP autoreset, TimeLimit 500).  Parity with gymnasium's own
     episodes is unpinned (reset draws use a counter hash, not PCG64)."""
 
-    device_native = True
     env_kind = GS_ENV_CARTPOLE       # gs_rollout_env's kind: one-launch rollouts when the policy fits in LDS
 
     def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, wrappers=(), device="cuda", **_):
@@ -90,29 +123,20 @@ class DeviceCartPoleVecEnv:
         CartPoleV1_RewardShaper (CartPole-v1:ppo_rewardshaped), which the gs_cartpole_shaped_*
         entries apply on the env's own thread with its previous potential in `prev_phi` (N) f64.
         Without a shaper the env calls the unshaped entries and has no prev_phi."""
-        self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 4, 2
-        self.seed, self.env_offset, self.max_steps = int(seed), int(env_offset), int(max_steps)
-        self.obs_shape, self.obs_dtype = (4,), torch.float32
-        self.device = torch.device(device)
+        N, z = self._alloc(n_envs, 4, 2, seed, env_offset, device)
+        self.max_steps = int(max_steps)
         self.wrappers = [dict(w) for w in (wrappers or ())]
         resolved = resolve_cartpole_wrappers(self.wrappers)
         if resolved is None:
             raise ValueError(f"the device CartPole-v1 does not apply env_wrappers={self.wrappers!r} "
                              "(gsamd.config.resolve_cartpole_wrappers)")
         self.wrappers_c, self.prev_phi = None, None
-        N, z = self.num_envs, dict(device=self.device)
         if resolved:
             kw = resolved[0][1]
             self.wrappers_c = CartPoleWrappers(1, int(kw["clip_potential"]), float(kw["angle_reward_scale"]),
                                                float(kw["position_reward_scale"]))
             self.prev_phi = torch.zeros(N, dtype=torch.float64, **z)
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)
-        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)
-        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
-        self.obs = torch.zeros(N, 4, dtype=torch.float32, **z)
-        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
-        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
-        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
 
     def reset(self):
         if self.wrappers_c is not None:
@@ -131,40 +155,40 @@ class DeviceCartPoleVecEnv:
             check(lib.gs_cartpole_shaped_step(ptr(self.state), ptr(self.prev_phi), ptr(self.meta), ptr(self.ep_ret),
                                               ptr(self.obs), self.wrappers_c, ptr(actions), self.num_envs,
                                               self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                              ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count),
-                                              ptr(self.ep_ret_sum), ptr(self.ep_len_sum), stream_handle()),
-                  "gs_cartpole_shaped_step")
+                                              ptr(dones_row), ptr(timeouts_row), *self._episode_counters(),
+                                              stream_handle()), "gs_cartpole_shaped_step")
             return
         check(lib.gs_cartpole_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), ptr(actions),
                                    self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                   ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
-                                   ptr(self.ep_len_sum), stream_handle()), "gs_cartpole_step")
+                                   ptr(dones_row), ptr(timeouts_row), *self._episode_counters(), stream_handle()),
+              "gs_cartpole_step")
+
+    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
+        head = self._policy_args(pm, buf, mode, rng_seed, counter0)
+        tail = (self.max_steps, self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf))
+        if self.wrappers_c is not None:          # the reward shaper rides along
+            check(lib.gs_rollout_cartpole_shaped(*head, ptr(self.state), ptr(self.prev_phi), ptr(self.meta),
+                                                 ptr(self.ep_ret), ptr(self.obs), self.wrappers_c, *tail),
+                  "gs_rollout_cartpole_shaped")
+            return
+        check(lib.gs_rollout_env(*head, int(self.env_kind), ptr(self.state), ptr(self.meta), ptr(self.ep_ret),
+                                 ptr(self.obs), *tail), "gs_rollout_env")
 
 
-class DeviceAcrobotVecEnv:
+class DeviceAcrobotVecEnv(DeviceVecEnv):
     """Acrobot-v1 on device (gymnasium 1.x "book" dynamics restated in
     csrc/gs_acrobot_env.h: RK4 of dt 0.2 in double precision, NEXT_STEP autoreset, TimeLimit 500).
     Parity with gymnasium's own episodes is unpinned (reset draws use a counter hash, not PCG64)."""
 
-    device_native = True
     env_kind = GS_ENV_ACROBOT
     # One-launch rollouts are the default only up to this many envs: past it the graph-replayed
     # step loop measured faster (DESIGN.md §4.1, profiles/acrobot_collect.json).  None = always.
     one_launch_max_envs = None
 
     def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, device="cuda", **_):
-        self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 6, 3
-        self.seed, self.env_offset, self.max_steps = int(seed), int(env_offset), int(max_steps)
-        self.obs_shape, self.obs_dtype = (6,), torch.float32
-        self.device = torch.device(device)
-        N, z = self.num_envs, dict(device=self.device)
+        N, z = self._alloc(n_envs, 6, 3, seed, env_offset, device)
+        self.max_steps = int(max_steps)
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)      # theta1, theta2, omega1, omega2
-        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
-        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
-        self.obs = torch.zeros(N, 6, dtype=torch.float32, **z)
-        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
-        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
-        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
 
     def reset(self):
         check(lib.gs_acrobot_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.num_envs,
@@ -176,8 +200,14 @@ class DeviceAcrobotVecEnv:
             raise ValueError("Acrobot dynamics need the step's actions")
         check(lib.gs_acrobot_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), ptr(actions),
                                   self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                  ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
-                                  ptr(self.ep_len_sum), stream_handle()), "gs_acrobot_step")
+                                  ptr(dones_row), ptr(timeouts_row), *self._episode_counters(), stream_handle()),
+              "gs_acrobot_step")
+
+    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
+        check(lib.gs_rollout_env(*self._policy_args(pm, buf, mode, rng_seed, counter0), int(self.env_kind),
+                                 ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.max_steps,
+                                 self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf)),
+              "gs_rollout_env")
 
 
 def mountaincar_wrappers_struct(wrappers) -> MountainCarWrappers:
@@ -203,7 +233,7 @@ def mountaincar_wrappers_struct(wrappers) -> MountainCarWrappers:
     return w
 
 
-class DeviceMountainCarVecEnv:
+class DeviceMountainCarVecEnv(DeviceVecEnv):
     """MountainCar-v0 on device with the reference's reward shaper / state-count bonus wrappers
     (csrc/gs_mountaincar_env.h: gymnasium 1.x dynamics in double precision,
     NEXT_STEP autoreset, TimeLimit 200; the wrappers in double on the float32 observation, in list
@@ -213,30 +243,20 @@ class DeviceMountainCarVecEnv:
     use a counter hash, not PCG64); the wrappers' arithmetic is pinned to the reference's classes
     (tests/golden/mountaincar_wrappers.npz).  The wrappers' info diagnostics are not reproduced."""
 
-    device_native = True
     env_kind = GS_ENV_MOUNTAINCAR
     # One-launch rollouts are the default only up to this many envs: past it the graph-replayed
     # step loop measured faster (DESIGN.md §4.1, profiles/mountaincar_collect.json).  None = always.
     one_launch_max_envs = None
 
     def __init__(self, n_envs, seed=42, env_offset=0, max_steps=200, wrappers=(), device="cuda", **_):
-        self.num_envs, self.obs_dim, self.n_actions = int(n_envs), 2, 3
-        self.seed, self.env_offset, self.max_steps = int(seed), int(env_offset), int(max_steps)
-        self.obs_shape, self.obs_dtype = (2,), torch.float32
-        self.device = torch.device(device)
+        N, z = self._alloc(n_envs, 2, 3, seed, env_offset, device)
+        self.max_steps = int(max_steps)
         self.wrappers = [dict(w) for w in (wrappers or ())]
         self.wrappers_c = mountaincar_wrappers_struct(self.wrappers)
         cells = self.wrappers_c.position_bins * self.wrappers_c.velocity_bins \
             if GS_MC_WRAP_BONUS in tuple(self.wrappers_c.order) else 0
-        N, z = self.num_envs, dict(device=self.device)
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)      # p, v, prev obs p, prev obs v
-        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
-        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
-        self.obs = torch.zeros(N, 2, dtype=torch.float32, **z)
         self.counts = torch.zeros(N, cells, dtype=torch.int32, **z)
-        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
-        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
-        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
 
     def _counts_ptr(self):
         return ptr(self.counts) if self.counts.numel() else None
@@ -253,11 +273,18 @@ class DeviceMountainCarVecEnv:
         check(lib.gs_mountaincar_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs),
                                       self._counts_ptr(), self.wrappers_c, ptr(actions), self.num_envs,
                                       self.max_steps, self.seed, self.env_offset, ptr(rewards_row), ptr(dones_row),
-                                      ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
-                                      ptr(self.ep_len_sum), stream_handle()), "gs_mountaincar_step")
+                                      ptr(timeouts_row), *self._episode_counters(), stream_handle()),
+              "gs_mountaincar_step")
+
+    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
+        """Its count tables and wrappers ride along."""
+        check(lib.gs_rollout_mountaincar(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
+                                         ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self._counts_ptr(),
+                                         self.wrappers_c, self.max_steps, self.seed, self.env_offset,
+                                         *self._episode_counters(), *self._row_args(buf)), "gs_rollout_mountaincar")
 
 
-class DeviceBanditVecEnv:
+class DeviceBanditVecEnv(DeviceVecEnv):
     """Bandit-v0 on device (csrc/gs_bandit_env.h restates the reference's
     gym_envs/mab_env.py MultiArmedBanditEnv): a stateless Gaussian bandit whose observation is
     zeros(n_arms), reward mean[a] + std[a] z, terminated after episode_length steps, NEXT_STEP
@@ -267,7 +294,6 @@ class DeviceBanditVecEnv:
     Parity with the reference's reward stream is unpinned (the normal draw is Box-Muller on the
     counter hash, not numpy's PCG64 ziggurat)."""
 
-    device_native = True
     env_kind = GS_ENV_BANDIT         # one-launch rollouts up to GS_BANDIT_ROLLOUT_MAX_ARMS arms
     one_launch_max_envs = None
 
@@ -283,23 +309,13 @@ class DeviceBanditVecEnv:
             raise ValueError("means / stds must have n_arms entries")
         if not (np.isfinite(m).all() and np.isfinite(s).all() and (s >= 0).all()):
             raise ValueError("means must be finite, stds finite and >= 0")
-        self.num_envs, self.obs_dim, self.n_actions, self.n_arms = int(n_envs), n, n, n
-        self.means, self.stds, self.episode_length = m, s, int(episode_length)
-        self.seed, self.env_offset = int(seed), int(env_offset)
+        self._alloc(n_envs, n, n, seed, env_offset, device)
+        self.n_arms, self.means, self.stds, self.episode_length = n, m, s, int(episode_length)
         self.max_steps = int(max_steps if max_steps else episode_length)
-        self.obs_shape, self.obs_dtype = (n,), torch.float32
-        self.device = torch.device(device)
         self.spec = BanditSpec()
         self.spec.n_arms, self.spec.episode_length = n, self.episode_length
         for a in range(n):
             self.spec.means[a], self.spec.stds[a] = float(m[a]), float(s[a])
-        N, z = self.num_envs, dict(device=self.device)
-        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
-        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
-        self.obs = torch.zeros(N, n, dtype=torch.float32, **z)
-        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
-        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
-        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
 
     def reset(self):
         check(lib.gs_bandit_reset(ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, self.num_envs,
@@ -311,11 +327,17 @@ class DeviceBanditVecEnv:
             raise ValueError("the bandit needs the step's actions")
         check(lib.gs_bandit_step(ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, ptr(actions),
                                  self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                 ptr(dones_row), ptr(timeouts_row), ptr(self.ep_count), ptr(self.ep_ret_sum),
-                                 ptr(self.ep_len_sum), stream_handle()), "gs_bandit_step")
+                                 ptr(dones_row), ptr(timeouts_row), *self._episode_counters(), stream_handle()),
+              "gs_bandit_step")
+
+    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
+        check(lib.gs_rollout_bandit(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.meta),
+                                    ptr(self.ep_ret), ptr(self.obs), self.spec, self.max_steps, self.seed,
+                                    self.env_offset, *self._episode_counters(), *self._row_args(buf)),
+              "gs_rollout_bandit")
 
 
-class DeviceTabularVecEnv:
+class DeviceTabularVecEnv(DeviceVecEnv):
     """A tabular env on device (csrc/gs_tabular.hip): FrozenLake-v1 (`kind` "frozenlake", 4x4 or
     8x8, slippery or not) or Taxi-v3 ("taxi") on gsamd.toytext's tables, or any (next, reward,
     term, starts, n_states, n_actions, K) passed as `tables`.  The observation is the reference's
@@ -324,8 +346,6 @@ class DeviceTabularVecEnv:
     uploaded once, here.  No env_kind: a one-hidden-layer policy has no one-launch rollout, the
     collector replays its step graph.  Parity with gymnasium's own episodes is unpinned (the
     outcome and reset draws use the counter hash, not PCG64)."""
-
-    device_native = True
 
     def __init__(self, n_envs, kind="frozenlake", encoding="binary", map_name="4x4", is_slippery=True, seed=42,
                  env_offset=0, max_steps=None, tables=None, device="cuda", **_):
@@ -336,13 +356,9 @@ class DeviceTabularVecEnv:
         nxt, rew, term, starts, S, A, K = tables if tables is not None else toytext.tables_for(
             kind, map_name, bool(is_slippery))
         self.kind, self.encoding = str(kind), str(encoding)
-        self.num_envs, self.n_states, self.n_actions, self.n_outcomes = int(n_envs), int(S), int(A), int(K)
-        self.obs_dim = discrete_encoding_dim(self.encoding, self.n_states)
-        self.seed, self.env_offset = int(seed), int(env_offset)
+        self.n_states, self.n_outcomes = int(S), int(K)
+        N, z = self._alloc(n_envs, discrete_encoding_dim(self.encoding, self.n_states), A, seed, env_offset, device)
         self.max_steps = int(max_steps if max_steps else toytext.MAX_EPISODE_STEPS.get(self.kind, 100))
-        self.obs_shape, self.obs_dtype = (self.obs_dim,), torch.float32
-        self.device = torch.device(device)
-        N, z = self.num_envs, dict(device=self.device)
         shape = (self.n_states, self.n_actions, self.n_outcomes)
         self.next_table = torch.as_tensor(np.ascontiguousarray(nxt, np.int32).reshape(shape)).to(self.device)
         self.reward_table = torch.as_tensor(np.ascontiguousarray(rew, np.float32).reshape(shape)).to(self.device)
@@ -351,12 +367,6 @@ class DeviceTabularVecEnv:
         self.spec = TabularSpec(self.n_states, self.n_actions, self.n_outcomes, int(self.starts.numel()),
                                 GS_ENCODINGS[self.encoding], self.obs_dim)
         self.state = torch.zeros(N, dtype=torch.int32, **z)
-        self.meta = torch.zeros(N, 3, dtype=torch.int32, **z)         # steps, episodes, pending
-        self.ep_ret = torch.zeros(N, dtype=torch.float32, **z)
-        self.obs = torch.zeros(N, self.obs_dim, dtype=torch.float32, **z)
-        self.ep_count = torch.zeros(N, dtype=torch.int32, **z)
-        self.ep_ret_sum = torch.zeros(N, dtype=torch.float32, **z)
-        self.ep_len_sum = torch.zeros(N, dtype=torch.float32, **z)
 
     def reset(self):
         check(lib.gs_tabular_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
@@ -371,8 +381,7 @@ class DeviceTabularVecEnv:
                                   ptr(self.next_table), ptr(self.reward_table), ptr(self.term_table),
                                   ptr(self.starts), ptr(actions), self.num_envs, self.max_steps, self.seed,
                                   self.env_offset, ptr(rewards_row), ptr(dones_row), ptr(timeouts_row),
-                                  ptr(self.ep_count), ptr(self.ep_ret_sum), ptr(self.ep_len_sum), stream_handle()),
-              "gs_tabular_step")
+                                  *self._episode_counters(), stream_handle()), "gs_tabular_step")
 
 
 class DeviceRolloutBuffer:
@@ -658,49 +667,8 @@ class DeviceRolloutCollector:
 
     def _collect_one_launch(self, mode):
         """The T vector steps as one launch (policy act + env step per step, envs resident in
-        LDS): gs_rollout_env for an env with real dynamics, else gs_rollout_synth, after which
-        the synthetic env's host step counter advances by T."""
-        buf, pm, env = self._buffer, self.policy_model, self.env
-        if isinstance(env, DeviceMountainCarVecEnv):     # its count tables and wrappers ride along
-            check(lib.gs_rollout_mountaincar(
-                ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed, self.total_vec_steps,
-                ptr(env.state), ptr(env.meta), ptr(env.ep_ret), ptr(env.obs), env._counts_ptr(), env.wrappers_c,
-                env.max_steps, env.seed, env.env_offset, ptr(env.ep_count), ptr(env.ep_ret_sum),
-                ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values),
-                ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_mountaincar")
-            return
-        if isinstance(env, DeviceCartPoleVecEnv) and env.wrappers_c is not None:     # the reward shaper rides along
-            check(lib.gs_rollout_cartpole_shaped(
-                ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed, self.total_vec_steps,
-                ptr(env.state), ptr(env.prev_phi), ptr(env.meta), ptr(env.ep_ret), ptr(env.obs), env.wrappers_c,
-                env.max_steps, env.seed, env.env_offset, ptr(env.ep_count), ptr(env.ep_ret_sum),
-                ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values),
-                ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_cartpole_shaped")
-            return
-        if isinstance(env, DeviceBanditVecEnv):
-            check(lib.gs_rollout_bandit(
-                ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed, self.total_vec_steps,
-                ptr(env.meta), ptr(env.ep_ret), ptr(env.obs), env.spec, env.max_steps, env.seed, env.env_offset,
-                ptr(env.ep_count), ptr(env.ep_ret_sum), ptr(env.ep_len_sum), ptr(buf.obs), ptr(buf.actions),
-                ptr(buf.logprobs), ptr(buf.values), ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts),
-                stream_handle()), "gs_rollout_bandit")
-            return
-        if not isinstance(env, DeviceSyntheticVecEnv):
-            check(lib.gs_rollout_env(ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed,
-                                     self.total_vec_steps, int(env.env_kind), ptr(env.state), ptr(env.meta),
-                                     ptr(env.ep_ret), ptr(env.obs), env.max_steps, env.seed, env.env_offset,
-                                     ptr(env.ep_count), ptr(env.ep_ret_sum), ptr(env.ep_len_sum), ptr(buf.obs),
-                                     ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values), ptr(buf.rewards),
-                                     ptr(buf.dones), ptr(buf.timeouts), stream_handle()), "gs_rollout_env")
-            return
-        check(lib.gs_rollout_synth(ptr(pm.params), pm.dims, self.n_envs, self.n_steps, int(mode), self.rng_seed,
-                                   self.total_vec_steps, ptr(env.state), ptr(env.ep_ret), ptr(env.obs),
-                                   env.episode_len, env.truncate_every, env.reward, env.seed, env.env_offset,
-                                   env.step_count, ptr(env.ep_count), ptr(env.ep_ret_sum), ptr(env.ep_len_sum),
-                                   ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values),
-                                   ptr(buf.rewards), ptr(buf.dones), ptr(buf.timeouts), stream_handle()),
-              "gs_rollout_synth")
-        env.step_count += self.n_steps
+        LDS): the env's own gs_rollout_* call (rollout_into)."""
+        self.env.rollout_into(self.policy_model, self._buffer, mode, self.rng_seed, self.total_vec_steps)
 
     def _steps_into_buffer(self, mode, clock=None):
         """The rollout's T vector steps on a device env: policy act (writes the step's obs /

@@ -1,5 +1,5 @@
 """Test helper: the reference's CartPoleV1_RewardShaper arithmetic (gym_wrappers/CartPoleV1/
-reward_shaper.py) restated in Python floats, the twin of cartpole_phi / cartpole_shaped_env_step in
+reward_shaper.py) restated in Python floats, the twin of cartpole_phi / CartPoleShapedEnv in
 csrc/gs_cartpole_env.h.  tests/golden/cartpole_shaper.npz pins it to the class bit for bit
 (test_cartpole_bandit_cpu.py); the GPU test then uses it where the fixture cannot reach (envs whose
 reset hash is not the fixture's).

@@ -22,7 +22,7 @@ def _mix64(x: int) -> int:
 
 
 def reset_unit(seed: int, env: int, episode: int) -> float:
-    """env_reset_unit(seed, env, episode, 0) of csrc/gs_cartpole_env.h."""
+    """env_reset_unit(seed, env, episode, 0) of csrc/gs_env_episode.h."""
     h = _mix64(_mix64(_mix64(_mix64(seed) ^ env) ^ episode) ^ 0xC0)
     return (h >> 11) * UNIT
 
