@@ -329,11 +329,17 @@ int launch_heads_act(const float *P, const Layout &L, const float *zpart, int64_
                      const uint64_t *clock = nullptr);
 int launch_loss(const float *P, const Layout &L, int64_t B, const Workspace &ws, const LossArgs &la, float *metrics,
                 int32_t *stop, hipStream_t s);
-size_t bwd_lds_bytes(const Layout &L, int64_t B);
+// nt: threads per workgroup (512: the single-GPU chain entry's eight waves keep more partial tiles)
+size_t bwd_lds_bytes(const Layout &L, int64_t B, int nt = 256);
 int prepare_kernels(const Layout &L, int64_t B);
+// Threads per workgroup of the single-GPU chain entry k_bwd_chain: 512, or 256 with GS_BWD_NT=256 in
+// the environment (the same bits: the A/B arm and the tests' reference); gs_ppo_update reads it once
+// per call
+int bwd_chain_threads();
+// chain_nt: k_bwd_chain's threads per workgroup (0: bwd_chain_threads()); the k_bwd entries run 256
 int launch_bwd(const float *P, const Layout &L, int64_t B, const Workspace &ws, float *G, const int32_t *stop,
                hipStream_t s, const FusedFwd *ff = nullptr, const LossArgs *la = nullptr,
-               const BwdXchg *bx = nullptr);
+               const BwdXchg *bx = nullptr, int chain_nt = 0);
 // whether k_bwd's in-kernel exchange covers this shape (grid and per-workgroup slot limits, and
 // co-residency with `colocated` ranks sharing the GPU)
 bool bwd_xchg_fits(const Layout &L, int64_t B, int colocated = 1);

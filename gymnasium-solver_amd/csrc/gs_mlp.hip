@@ -34,6 +34,8 @@
 //   k_clip_adam   : global grad norm from the per-tile sums (identical in every
 //                   workgroup), clip coefficient, torch.optim.Adam update
 #include <float.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include <mutex>
 #include <type_traits>
@@ -1554,9 +1556,11 @@ struct BwdShape {
     }
 };
 
-size_t bwd_lds_bytes(const Layout &L, int64_t B)
+size_t bwd_lds_bytes(const Layout &L, int64_t B, int nt)
 {
     const int kRowsB = rows_b(L, B);
+    // 512 threads (k_bwd_chain): role B's kred and role C's partC hold one partial tile per wave
+    const int64_t wtiles = nt == 512 ? 2048 : 1024;
     const int A1 = L.A + 1;
     const int64_t Bp64 = (B + 63) / 64 * 64, Bp16 = (B + 15) / 16 * 16;
     const int64_t H2p = (L.H2 + 63) / 64 * 64;
@@ -1570,9 +1574,9 @@ size_t bwd_lds_bytes(const Layout &L, int64_t B)
                           Bp64 + (fastA ? 0 : 816);
     const int64_t roleB = (regsB ? (int64_t)round4(kRowsB / 16 * 16 * (L.D + 1)) : (int64_t)kRowsB * (H2p + 4)) +
                           kTile * (H2p + 4) + round4(A1 * L.H2) + round4(kRowsB * A1) +
-                          kRowsB * 16 + round4(kRowsB * L.D) + kRowsB * 17 + 1024 +
+                          kRowsB * 16 + round4(kRowsB * L.D) + kRowsB * 17 + wtiles +
                           (int64_t)kRowsB * n_col_blocks(L.H2);
-    const int64_t roleC = Bp16 * 17 + round4((int)Bp16 * A1) + (A1 * 256 > 1024 ? A1 * 256 : 1024) + 2 +
+    const int64_t roleC = Bp16 * 17 + round4((int)Bp16 * A1) + (A1 * 256 > wtiles ? A1 * 256 : wtiles) + 2 +
                           (int64_t)metric_groups_per_wg((int)B / kTile, shp.nC) * kTile * kNumSums * 2;
     int64_t m = roleA;
     if (roleB > m) m = roleB;
@@ -1641,7 +1645,20 @@ __device__ __forceinline__ void store_metric_groups(const double *dscr, int n, i
 // in-backward xGMI exchange) and k_bwd_chain (the single-GPU fused chain, below).  XCHG: the entry
 // carries a BwdXchg; BASE: a chunked graph replay (k_local + the chunk's device step base).  A
 // FUSED body never loads a stop flag.
-template <class S, bool FUSED, bool XCHG, bool BASE>
+// NT: threads per workgroup.  256: four waves, every thread takes part in every phase.  512 (k_bwd_chain
+// only: compile-time shapes on the register-dh2 paths): waves 4-7 sit beside waves 0-3 on the four
+// SIMDs, so one wave's LDS / VALU / MFMA latencies are covered by its partner's issue.  The work is
+// divided so that no bit changes (W8 below): every MFMA accumulator sees the operand sequence of the
+// 256-thread body, partials are added in its order and association, and the block reductions keep
+// their 256-thread grouping (threads 256.. contribute nothing).
+//   role A  load: waves 4-7 the mask words, the h1 tile (transposed LDS stores) and the head block,
+//           waves 0-3 the loss rows; MFMA: wave w + 4 takes dW2 tile 1 of wave w's K range (ka == 2),
+//           wave w tile 0 and the db2 partial.
+//   role B  load: waves 0-6 the slab's operands, wave 7 the loss rows; MFMA (fp32): wave w + 4 takes
+//           the acc1 chain (elements 1, 3) of wave w's chunks, the join acc0 + acc1 goes through
+//           kred (8 partial tiles).  bf16 has one chain per tile: waves 4-7 pass.
+//   role C  load: waves 4-7 the h2 tile, waves 0-3 the loss rows; MFMA: as role B, through partC.
+template <class S, bool FUSED, bool XCHG, bool BASE, int NT = 256>
 __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layout &Lrt, int Brt,
                                          const float *__restrict__ x, const float *__restrict__ h1,
                                          const float *__restrict__ h2, const float *__restrict__ dz,
@@ -1671,8 +1688,14 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
     const int D = L.D, H1 = L.H1, H2 = L.H2, A = L.A, A1 = A + 1;
     constexpr int kRowsB = S::RB;      // this shape's role-B slab height (shadows the default)
     const BwdShape sh = BwdShape::make(L, B, kRowsB);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = NT == 512 ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;   // 512: scalar branches
     const int li = lane & 15, lq = lane >> 4;
+    static_assert(NT == 256 || NT == 512, "k_bwd: 256 or 512 threads");
+    constexpr bool W8 = NT == 512;
+    static_assert(!W8 || (FUSED && !XCHG && S::H1c > 0 && S::Bc > 0), "eight waves: the chain entry only");
+    // W8: the wave (0-3) whose K range / row tile this wave shares, and its half of that wave's work
+    const int cw = W8 ? wave & 3 : wave, hi = W8 ? wave >> 2 : 0;
     // dispatch order: role B (the longest) first, then A, then C; bid keeps the A, B, C numbering
     int bid = (int)blockIdx.x;
     if (bid < sh.nB) bid += sh.nA;
@@ -1686,7 +1709,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
         GS_STAMP_BEGIN_IF(2, bid == 0)
         const int Bp = (B + 63) / 64 * 64;      // padded K (batch) for 4 waves x 16
         const int ld = Bp + 4;
-        const bool fast = A1 <= 5;                   // dh2 in registers (no dh2 tile)
+        const bool fast = W8 || A1 <= 5;             // dh2 in registers (no dh2 tile); W8: k_bwd_chain asserts it
         float *dzs = lds;                            // [B][A1]
         float *whs = dzs + round4(B * A1);           // [A1][16]
         float *dh2T = whs + round4(A1 * 16);         // [16][Bp+4]  (n, b): h2 first, then dh2 (!fast)
@@ -1702,6 +1725,55 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
             constexpr int cB = S::Bc, cBp = (cB + 63) / 64 * 64, cncb = (Lc.H2 + kTile - 1) / kTile;
             constexpr int cka = (Lc.H1 / kTile) % 2 == 0 ? 2 : 1, ckw = kTile * cka, cq = ckw / 4;
             constexpr int NMk = (cBp + 255) / 256, NH1 = (cBp * cq + 255) / 256;
+            if constexpr (W8) {
+                // eight waves: waves 4-7 (lt = 0..255) run the 256-thread loader's loads and LDS stores,
+                // waves 0-3 only the loss rows, whose loads then wait for no tile
+                if (wave >= 4) {
+                    const int lt = tid - 256;
+                    int mr[NMk];
+                    float4 hr[NH1];
+#pragma unroll
+                    for (int j = 0; j < NMk; ++j) {
+                        const int b = lt + 256 * j;
+                        mr[j] = (int)h2mask[(int64_t)min(b, cB - 1) * cncb + nb];
+                    }
+#ifdef GS_STAMPS
+                    const unsigned long long t_ld0 = __builtin_amdgcn_s_memtime();
+#endif
+#pragma unroll
+                    for (int j = 0; j < NH1; ++j) {
+                        const int u = lt + 256 * j, b = u / cq, c4 = u % cq;
+                        hr[j] = *reinterpret_cast<const float4 *>(h1 + (int64_t)min(b, cB - 1) * Lc.H1 +
+                                                                  min(k0 + 4 * c4, Lc.H1 - 4));
+                    }
+                    const float wh = P[L.head_row(min(lt >> 4, A1 - 1)) + min(n0 + (lt & 15), H2 - 1)];
+                    if (lt < A1 * kTile) whs[lt] = n0 + (lt & 15) < H2 ? wh : 0.0f;
+#pragma unroll
+                    for (int j = 0; j < NMk; ++j)
+                        if (lt + 256 * j < cBp) mkA[lt + 256 * j] = lt + 256 * j < cB ? mr[j] : 0;
+#pragma unroll
+                    for (int j = 0; j < NH1; ++j) {
+                        const int u = lt + 256 * j, b = u / cq, c4 = u % cq;
+                        if (u < cBp * cq) {
+                            const bool ok = b < cB && k0 + 4 * c4 < Lc.H1;
+                            h1T[(4 * c4 + 0) * ld + b] = ok ? hr[j].x : 0.0f;
+                            h1T[(4 * c4 + 1) * ld + b] = ok ? hr[j].y : 0.0f;
+                            h1T[(4 * c4 + 2) * ld + b] = ok ? hr[j].z : 0.0f;
+                            h1T[(4 * c4 + 3) * ld + b] = ok ? hr[j].w : 0.0f;
+                        }
+                    }
+#ifdef GS_STAMPS
+                    if (bid == 0 && lt == 0) {      // loader wave: entry -> first tile load, -> tile in LDS
+                        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                        atomicAdd(&g_stamp_acc[2][13], t_ld0 - _st_t0);
+                        atomicAdd(&g_stamp_acc[2][14], __builtin_amdgcn_s_memtime() - _st_t0);
+                    }
+#endif
+                } else {
+                    GS_STAMP_ENTRY
+                    loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, 0, B, dzs, nullptr);
+                }
+            } else {
             int mr[NMk];
             float4 hr[NH1];
             float wh = 0.0f;
@@ -1742,6 +1814,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                     h1T[(4 * c4 + 3) * ld + b] = ok ? hr[j].w : 0.0f;
                 }
             }
+            }
         } else {
             if constexpr (FUSED)
                 loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, 0, B, dzs, nullptr);
@@ -1768,7 +1841,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
         __syncthreads();
         GS_STAMP(0)
         const int nch = Bp / kTile;
-        const int ch0 = (wave * nch) / 4, ch1 = ((wave + 1) * nch) / 4;
+        const int ch0 = (cw * nch) / 4, ch1 = ((cw + 1) * nch) / 4;
         // the ka dW2 tiles; k-block-0 workgroups also form db2[n] = sum_b dh2[b, n]: from the A
         // operands they already hold (fast path), or as an MFMA against a ones operand (t == ka)
         const int nt = sh.ka + (!fast && kb == 0 ? 1 : 0);
@@ -1794,6 +1867,52 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                     av[c] = (mkA[b + c] >> li) & 1 ? sacc : 0.0f;
                 }
             };
+            if constexpr (W8) {
+                // wave w + 4 accumulates tile 1 of wave w's K range, wave w tile 0 and the db2 partial:
+                // each tile's accumulators see the 256-thread loop's operands in its order (both waves
+                // form the chunk's dh2 operand).  ka == 1: waves 4-7 pass.
+                if (hi < nt) {
+                    const float *hb = h1T + (hi * kTile + li) * ld;
+                    const bool dsm = kb == 0 && hi == 0;
+                    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = {0.f, 0.f, 0.f, 0.f};
+                    if constexpr (S::BF) {
+                        const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll 2
+                        for (int ch = ch0; ch < ch1; ch += 2) {
+                            const int b = ch * kTile + 4 * lq;
+                            const bool two = ch + 1 < ch1;
+                            float av0[4], av1[4] = {0.f, 0.f, 0.f, 0.f};
+                            dh2_rows(b, av0);
+                            if (two) dh2_rows(b + kTile, av1);
+                            if (dsm) {
+                                dsum = (((dsum + av0[0]) + av0[1]) + av0[2]) + av0[3];
+                                dsum = (((dsum + av1[0]) + av1[1]) + av1[2]) + av1[3];
+                            }
+                            const float4 bb0 = *reinterpret_cast<const float4 *>(hb + b);
+                            const float4 bb1 = two ? *reinterpret_cast<const float4 *>(hb + b + kTile) : z4;
+                            a0 = mfma_bf16_pair(f4(av0), f4(av1), bb0, bb1, a0);
+                        }
+                    } else {
+#pragma unroll 2
+                        for (int ch = ch0; ch < ch1; ++ch) {
+                            const int b = ch * kTile + 4 * lq;
+                            float av[4];
+                            dh2_rows(b, av);
+                            if (dsm) dsum = (((dsum + av[0]) + av[1]) + av[2]) + av[3];
+                            const float4 bb = *reinterpret_cast<const float4 *>(hb + b);
+                            a0 = mfma4(av[0], bb.x, a0);
+                            a1 = mfma4(av[1], bb.y, a1);
+                            a0 = mfma4(av[2], bb.z, a0);
+                            a1 = mfma4(av[3], bb.w, a1);
+                        }
+                    }
+                    GS_STAMP(1)
+                    const f32x4 at = a0 + a1;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) red[(cw * 3 + hi) * 256 + (lq * 4 + r) * kTile + li] = at[r];
+                    if (dsm) red[(cw * 3 + 2) * 256 + lq * kTile + li] = dsum;   // slab 2 is free (nt <= 2)
+                }
+            } else {
             if constexpr (S::BF) {
                 // bf16 mode: chunk pairs (the fast path only has the ka dW2 tiles, no ones tile)
                 const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1845,6 +1964,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                 for (int r = 0; r < 4; ++r) red[(wave * 3 + t) * 256 + (lq * 4 + r) * kTile + li] = at[r];
             }
             if (kb == 0) red[(wave * 3 + 2) * 256 + lq * kTile + li] = dsum;   // slab 2 is free (nt <= 2)
+            }
         } else {
             // dh2 = relu'(h2) * (dz . Wh), in place; lane owns hidden unit i, rows stride 16
             {
@@ -1895,6 +2015,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                 const int j = t < sh.ka ? t : 2;
                 gv[j] = g;
                 ok[j] = t < sh.ka ? (n0 + row < H2 && k0 + t * kTile + col < H1) : (col == 0 && n0 + row < H2);
+                if constexpr (W8) ok[j] = ok[j] && tid < 256;      // threads 256..: no element (row >= 16)
             }
             // db2 element of this thread: n0 + row (ones tile, col 0) or n0 + tid (fast path: the 16
             // (wave, lane group) partials of column tid, in order)
@@ -1950,7 +2071,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
         GS_STAMP_BEGIN_IF(4, bid == 0)
         const int H2p = (H2 + 63) / 64 * 64;
         const int ld = H2p + 4;
-        const bool dh2_regs = A1 <= 5 && H2 % 64 == 0;   // dh2 formed in registers, no dh2 slab
+        const bool dh2_regs = W8 || (A1 <= 5 && H2 % 64 == 0);   // dh2 formed in registers, no dh2 slab (W8: asserted)
         float *dh2s = lds;                          // [32][H2p+4]  dh2 (!dh2_regs); dW1 partial scratch
         float *W2T = dh2s + (dh2_regs ? round4(kRowsB / 16 * 16 * (D + 1)) : kRowsB * ld);   // [16][H2p+4]
         float *whs = W2T + kTile * ld;              // [A1][H2]
@@ -1958,11 +2079,11 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
         float *h1m = dzs + round4(kRowsB * A1);     // [64][16]
         float *xs = h1m + kRowsB * 16;              // [64][D]
         float *tile = xs + round4(kRowsB * D);      // [32][17]
-        float *kred = tile + kRowsB * 17;           // [4][256] K-half partial tiles
-        // waves 0-2 stream the slab's operands into LDS while wave 3 computes its loss rows
-        // (fused path): the loss math overlaps the loads instead of following them
-        constexpr int kLd = FUSED ? 192 : 256;
-        int *mkB = reinterpret_cast<int *>(kred + 1024);   // [32][ncb] relu'(h2) bits
+        float *kred = tile + kRowsB * 17;           // [4][256] K-half partial tiles (W8: [8][256], per chain)
+        // waves 0-2 (W8: 0-6) stream the slab's operands into LDS while the last wave computes its loss
+        // rows (fused path): the loss math overlaps the loads instead of following them
+        constexpr int kLd = FUSED ? NT - 64 : 256;
+        int *mkB = reinterpret_cast<int *>(kred + (W8 ? 2048 : 1024));   // [32][ncb] relu'(h2) bits
         if constexpr (S::H1c > 0 && S::Bc > 0) {
             // compile-time shapes: every operand load of the slab is issued before the first
             // LDS write (one memory round trip instead of one per operand loop)
@@ -1972,7 +2093,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
             constexpr int NM = (kRowsB * cncb + kLd - 1) / kLd, NW = (cH2p * 4 + kLd - 1) / kLd;
             constexpr int NH = (cA1 * cH2 + kLd - 1) / kLd, N1 = (kRowsB * 16 + kLd - 1) / kLd;
             constexpr int NX = (kRowsB * cD + kLd - 1) / kLd;
-            if (tid < kLd) {
+            if (W8 ? wave < NT / 64 - 1 : tid < kLd) {
                 int mr[NM];
                 float4 wr[NW];
                 float hr[NH], h1r[N1], xr[NX];
@@ -2068,7 +2189,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
         }
 #endif
         if constexpr (FUSED) {    // the kb == 0 slab also keeps its rows' metric sums
-            loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, b0, kRowsB, dzs, nullptr, kLd, 256 - kLd);
+            loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, b0, kRowsB, dzs, nullptr, kLd, NT - kLd);
         } else {
             for (int u = tid; u < kRowsB * A1; u += 256)
                 dzs[u] = b0 * A1 + u < B * A1 ? dz[(int64_t)b0 * A1 + u] : 0.0f;
@@ -2076,7 +2197,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
 #ifdef GS_STAMPS
         // (behind the braces above: an unbraced `else` after this block bound to its `if`, and the
         // stamp build's fused role B then also read dz, which the chain entry does not pass)
-        if (bid == 0 && tid == 192) {   // loss wave: its rows' loss + gradient
+        if (bid == 0 && tid == kLd) {   // loss wave: its rows' loss + gradient
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             atomicAdd(&g_stamp_acc[7][0], __builtin_amdgcn_s_memtime() - t_rb0);
             atomicAdd(&g_stamp_cnt[7], 1ull);
@@ -2088,7 +2209,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
         // 4 row tiles, one per wave over the whole K
         static_assert(kRowsB == 32 || kRowsB == 64, "role-B slabs of 32 or 64 rows");
         const int nchB = H2p / kTile;
-        const int rt = kRowsB == 64 ? wave : wave >> 1, half = kRowsB == 64 ? 0 : wave & 1;
+        const int rt = kRowsB == 64 ? cw : cw >> 1, half = kRowsB == 64 ? 0 : cw & 1;
         const int chb = half ? nchB / 2 : 0, che = (half || kRowsB == 64) ? nchB : nchB / 2;
         f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
         if (dh2_regs) {
@@ -2119,8 +2240,28 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                     av[j] = ((m >> j) & 1u) ? sacc : 0.0f;
                 }
             };
-            if constexpr (S::BF) {
+            if constexpr (W8 && !S::BF) {
+                // wave w + 4 runs the acc1 chain (elements 1, 3) of wave w's chunks, wave w the acc0
+                // chain (0, 2); each forms only its two operand elements and leaves its chain in acc0
+                auto chain = [&](auto sel) {
+                    constexpr int e = decltype(sel)::value;
+                    f32x4 a = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 2
+                    for (int ch = chb; ch < che; ++ch) {
+                        const int n = ch * kTile + 4 * lq;
+                        float av[4];
+                        dh2_cols(ch, av);
+                        const float4 w = *reinterpret_cast<const float4 *>(brow + n);
+                        a = mfma4(av[e], e ? w.y : w.x, a);
+                        a = mfma4(av[e + 2], e ? w.w : w.z, a);
+                    }
+                    return a;
+                };
+                if (hi) acc0 = chain(std::integral_constant<int, 1>{});
+                else acc0 = chain(std::integral_constant<int, 0>{});
+            } else if constexpr (S::BF) {
                 const float4 z4 = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (!W8 || hi == 0)      // one chain per tile: waves 4-7 pass
 #pragma unroll 2
                 for (int ch = chb; ch < che; ch += 2) {
                     const int n = ch * kTile + 4 * lq;
@@ -2232,6 +2373,26 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
             }
         }
         }
+        if constexpr (W8) {
+            // fp32: kred[w] = wave w's acc0 chain, kred[w + 4] its acc1 chain, joined here as the
+            // 256-thread body's acc0 + acc1; bf16: waves 0-3 only, as there
+            constexpr bool kPairs = !S::BF;
+            if (kPairs || hi == 0) {
+                f32x4 acc = acc0;
+                if constexpr (!kPairs) acc = acc0 + acc1;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) kred[wave * 256 + (lq * 4 + r) * kTile + li] = acc[r];
+            }
+            __syncthreads();
+            auto ktile = [&](int w, int e) { return kPairs ? kred[w * 256 + e] + kred[(w + 4) * 256 + e] : kred[w * 256 + e]; };
+            for (int u = tid; u < kRowsB * kTile; u += NT) {
+                const int row = u >> 4, col = u & 15;
+                const int t = row >> 4, rr = row & 15;
+                const float g = kRowsB == 64 ? ktile(t, rr * kTile + col)
+                                             : ktile(2 * t, rr * kTile + col) + ktile(2 * t + 1, rr * kTile + col);
+                tile[row * 17 + col] = h1m[row * 16 + col] > 0.0f ? g : 0.0f;   // relu'(h1)
+            }
+        } else {
         {
             const f32x4 acc = acc0 + acc1;
 #pragma unroll
@@ -2245,6 +2406,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                                          : kred[(2 * t) * 256 + rr * kTile + col] + kred[(2 * t + 1) * 256 + rr * kTile + col];
             tile[row * 17 + col] = h1m[row * 16 + col] > 0.0f ? g : 0.0f;   // relu'(h1)
         }
+        }
         __syncthreads();
         GS_STAMP(2)
         // dW1 / db1 partials over this slab's rows: row groups of 16, then combine in order
@@ -2252,7 +2414,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
             constexpr int ng = kRowsB / 16;
             float *pr = dh2s;                       // reuse: [ng][16*(D+1)]
             const int nout = kTile * (D + 1);
-            for (int u = tid; u < ng * nout; u += 256) {
+            for (int u = tid; u < ng * nout; u += NT) {
                 const int g = u / nout, o = u - g * nout;
                 const int col = o / (D + 1), d = o - col * (D + 1);
                 float s = 0.0f;
@@ -2284,7 +2446,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                     if (ok[j]) part1[((int64_t)rb * H1 + k0 + col) * (D + 1) + d] = pv[j];
                 }
             } else
-            for (int o = tid; o < nout; o += 256) {
+            for (int o = tid; o < nout; o += NT) {
                 const int col = o / (D + 1), d = o - col * (D + 1);
                 float t = 0.0f;
 #pragma unroll
@@ -2320,8 +2482,9 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                 }
             if (ge == 0) gs = 0;
         }
+        constexpr int kPartMin = W8 ? 2048 : 1024;      // partC: one 16x16 partial tile per wave
         double *dscrC = reinterpret_cast<double *>(
-            (reinterpret_cast<uintptr_t>(dzs + Bp * A1 + (A1 * 256 > 1024 ? A1 * 256 : 1024)) + 7) & ~(uintptr_t)7);
+            (reinterpret_cast<uintptr_t>(dzs + Bp * A1 + (A1 * 256 > kPartMin ? A1 * 256 : kPartMin)) + 7) & ~(uintptr_t)7);
         auto loss_in = [&]() {
             if constexpr (FUSED)
                 loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, 0, Bp, dzs, ge > gs ? dscrC : nullptr, 0, 256,
@@ -2333,6 +2496,44 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
             // compile-time shapes: the h2 column tile is in flight while the loss rows run
             constexpr Layout Lc = S::lay(Layout{});
             constexpr int cB = S::Bc, cBp = (cB + 15) / 16 * 16, NH = (cBp * 4 + 255) / 256;
+            if constexpr (W8) {
+                // eight waves: waves 4-7 (lt = 0..255) load and store the h2 tile — only they wait for the
+                // h2 pointer, which comes from the argument tail; waves 0-3 start on the loss rows at once
+                if (wave >= 4) {
+                    const int lt = tid - 256;
+                    float4 hr[NH];
+#pragma unroll
+                    for (int j = 0; j < NH; ++j) {
+                        const int u = lt + 256 * j, b = u >> 2, c4 = u & 3;
+                        hr[j] = *reinterpret_cast<const float4 *>(h2 + (int64_t)min(b, cB - 1) * Lc.H2 +
+                                                                  min(n0 + 4 * c4, Lc.H2 - 4));
+                    }
+#ifdef GS_STAMPS
+                    const unsigned long long t_ld0 = __builtin_amdgcn_s_memtime();
+#endif
+#pragma unroll
+                    for (int j = 0; j < NH; ++j) {
+                        const int u = lt + 256 * j, b = u >> 2, c4 = u & 3;
+                        if (u < cBp * 4) {
+                            const bool ok = b < cB && n0 + 4 * c4 < Lc.H2;
+                            hs[b * 17 + 4 * c4 + 0] = ok ? hr[j].x : 0.0f;
+                            hs[b * 17 + 4 * c4 + 1] = ok ? hr[j].y : 0.0f;
+                            hs[b * 17 + 4 * c4 + 2] = ok ? hr[j].z : 0.0f;
+                            hs[b * 17 + 4 * c4 + 3] = ok ? hr[j].w : 0.0f;
+                        }
+                    }
+#ifdef GS_STAMPS
+                    if (bid == 0 && lt == 0) {      // loader wave: entry -> tile loads issued, -> tile in LDS
+                        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+                        atomicAdd(&g_stamp_acc[5][13], t_ld0 - _st_t0);
+                        atomicAdd(&g_stamp_acc[5][14], __builtin_amdgcn_s_memtime() - _st_t0);
+                    }
+#endif
+                } else {
+                    GS_STAMP_ENTRY
+                    loss_in();
+                }
+            } else {
             float4 hr[NH];
 #pragma unroll
             for (int j = 0; j < NH; ++j) {      // clamped, unconditional; zeroed at the stores
@@ -2352,6 +2553,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                     hs[b * 17 + 4 * c4 + 2] = ok ? hr[j].z : 0.0f;
                     hs[b * 17 + 4 * c4 + 3] = ok ? hr[j].w : 0.0f;
                 }
+            }
             }
         } else {
 #pragma unroll 4
@@ -2383,7 +2585,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                 // in wave order through LDS
                 const int li = lane & 15, lq = lane >> 4;
                 const int nch = Bp / kTile;
-                const int ch0 = (wave * nch) / 4, ch1 = ((wave + 1) * nch) / 4;
+                const int ch0 = (cw * nch) / 4, ch1 = ((cw + 1) * nch) / 4;
                 f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
                 auto chunk = [&](int b, float (&av)[4], float (&bv)[4]) {
 #pragma unroll
@@ -2392,7 +2594,20 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                         bv[c] = hs[(b + c) * 17 + li];
                     }
                 };
-                if constexpr (S::BF) {
+                constexpr bool kPairs = W8 && !S::BF;   // partC[w] = wave w's acc0 chain, partC[w + 4] its acc1 chain
+                if constexpr (kPairs) {
+                    // wave w + 4 runs the acc1 chain (rows b + 1, b + 3 of wave w's chunks), wave w the
+                    // acc0 chain (b, b + 2); each reads only its two rows and leaves its chain in acc0
+                    const int e = hi;
+#pragma unroll 2
+                    for (int ch = ch0; ch < ch1; ++ch) {
+                        const int b = ch * kTile + 4 * lq + e;
+                        const float a0 = li < A1 ? dzs[b * A1 + li] : 0.0f, a2 = li < A1 ? dzs[(b + 2) * A1 + li] : 0.0f;
+                        acc0 = mfma4(a0, hs[b * 17 + li], acc0);
+                        acc0 = mfma4(a2, hs[(b + 2) * 17 + li], acc0);
+                    }
+                } else if constexpr (S::BF) {
+                    if (!W8 || hi == 0)      // one chain per tile: waves 4-7 pass
 #pragma unroll 2
                     for (int ch = ch0; ch < ch1; ch += 2) {
                         const int b = ch * kTile + 4 * lq;
@@ -2413,12 +2628,26 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                     acc1 = mfma4(av[3], bv[3], acc1);
                 }
                 }
+                if constexpr (W8) {
+                    // fp32: partC[w] = wave w's acc0 chain, partC[w + 4] its acc1 chain (joined below
+                    // as the 256-thread body's acc0 + acc1); bf16: waves 0-3 only, as there
+                    if (kPairs || hi == 0) {
+                        f32x4 acc = acc0;
+                        if constexpr (!kPairs) acc = acc0 + acc1;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) partC[wave * 256 + (lq * 4 + r) * kTile + li] = acc[r];
+                    }
+                } else {
                 const f32x4 acc = acc0 + acc1;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) partC[wave * 256 + (lq * 4 + r) * kTile + li] = acc[r];
+                }
                 __syncthreads();
                 const int a = tid >> 4, i = tid & 15;
-                float hv[1] = {tid < nout ? ((partC[tid] + partC[256 + tid]) + partC[512 + tid]) + partC[768 + tid]
+                float hv[1] = {tid < nout ? (kPairs ? (((partC[tid] + partC[1024 + tid]) + (partC[256 + tid] + partC[1280 + tid])) +
+                                                       (partC[512 + tid] + partC[1536 + tid])) +
+                                                          (partC[768 + tid] + partC[1792 + tid])
+                                                    : ((partC[tid] + partC[256 + tid]) + partC[512 + tid]) + partC[768 + tid])
                                           : 0.0f};
                 bool ok[1] = {tid < nout && n0 + i < H2};
                 if (xchg) bwd_exchange<1>(bx, xseq, hv, ok);
@@ -2522,20 +2751,28 @@ struct BwdTail {
     const int64_t *step_base;          // BASE only
     LossArgs la;
 };
-template <class S, bool BASE>
-__global__ __launch_bounds__(256) void k_bwd_chain(const float *__restrict__ P, const float *__restrict__ h1,
-                                                   const uint16_t *__restrict__ h2mask,
-                                                   const float *__restrict__ zpart, const float *__restrict__ fields,
-                                                   const float *__restrict__ x, int fstride, int k_local, BwdTail t)
+// NT = 512 (the default): eight waves, see bwd_body; NT = 256 (GS_BWD_NT=256): the k_bwd body, the same bits.
+// 512 threads: at most 4 waves per SIMD asked for (two workgroups per CU), so that the register budget is 128
+// VGPRs: at the default the scheduler holds a 512-thread kernel to 64 VGPRs for 8 waves per SIMD, and
+// the loss rows' load burst then comes out as three dependent groups.
+template <class S, bool BASE, int NT = 512>
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(NT == 512 ? 2 : 1, NT == 512 ? 4 : 8)))
+void k_bwd_chain(const float *__restrict__ P, const float *__restrict__ h1,
+                                                  const uint16_t *__restrict__ h2mask,
+                                                  const float *__restrict__ zpart, const float *__restrict__ fields,
+                                                  const float *__restrict__ x, int fstride, int k_local, BwdTail t)
 {
     static_assert(S::Bc > 0 && S::H1c > 0, "chain entry: compile-time shapes only");
+    // the eight-wave division covers the register-dh2 paths of roles A and B and role C's MFMA tile
+    static_assert(NT == 256 || (S::lay(Layout{}).A + 1 <= 5 && S::lay(Layout{}).H2 % 64 == 0),
+                  "chain entry with 512 threads: A + 1 <= 5 and H2 a multiple of 64");
     FusedFwd ff{};
     ff.fa = reinterpret_cast<const int32_t *>(fields);
     ff.folp = fields + fstride, ff.fov = fields + 2 * (int64_t)fstride;
     ff.fadv = fields + 3 * (int64_t)fstride, ff.fret = fields + 4 * (int64_t)fstride;
     ff.mpart = t.mpart, ff.headsq = t.headsq, ff.step_base = t.step_base, ff.k_local = k_local;
-    bwd_body<S, true, false, BASE>(P, Layout{}, S::Bc, x, h1, t.h2, nullptr, t.G, t.part1, t.sumsq, nullptr, zpart, ff,
-                                   t.la, h2mask, BwdXchg{});
+    bwd_body<S, true, false, BASE, NT>(P, Layout{}, S::Bc, x, h1, t.h2, nullptr, t.G, t.part1, t.sumsq, nullptr, zpart,
+                                       ff, t.la, h2mask, BwdXchg{});
 }
 
 // ------------------------------------------------------------------------------------
@@ -2850,6 +3087,24 @@ bool has_bf16_chain(const Layout &L, int64_t B)
     return ok && has_fused(L, B);
 }
 
+int bwd_chain_threads()
+{
+    const char *e = getenv("GS_BWD_NT");
+    return e && strcmp(e, "256") == 0 ? 256 : 512;
+}
+
+// the dynamic-LDS limits of k_bwd_chain's instantiations of shape S (both thread counts, both BASE)
+template <class S>
+static int set_chain_lds_limits(const Layout &L, int64_t B)
+{
+    const size_t l8 = bwd_lds_bytes(L, B, 512), l4 = bwd_lds_bytes(L, B, 256);
+    int r = set_lds_limit((const void *)k_bwd_chain<S, false, 512>, l8);
+    if (!r) r = set_lds_limit((const void *)k_bwd_chain<S, true, 512>, l8);
+    if (!r) r = set_lds_limit((const void *)k_bwd_chain<S, false, 256>, l4);
+    if (!r) r = set_lds_limit((const void *)k_bwd_chain<S, true, 256>, l4);
+    return r;
+}
+
 int prepare_kernels(const Layout &L, int64_t B)
 {
     if (has_bf16_chain(L, B)) {
@@ -2871,12 +3126,9 @@ int prepare_kernels(const Layout &L, int64_t B)
             const size_t lds = bwd_lds_bytes(L, B);
             int r = set_lds_limit((const void *)k_bwd<Sh, true>, lds);
             if constexpr (chain_shape<Sh>()) {
-                if (!r) r = set_lds_limit((const void *)k_bwd_chain<Sh, false>, lds);
-                if (!r) r = set_lds_limit((const void *)k_bwd_chain<Sh, true>, lds);
-                if constexpr (bf16_shape<Sh>()) {
-                    if (!r) r = set_lds_limit((const void *)k_bwd_chain<Bf16Shape<Sh>, false>, lds);
-                    if (!r) r = set_lds_limit((const void *)k_bwd_chain<Bf16Shape<Sh>, true>, lds);
-                }
+                if (!r) r = set_chain_lds_limits<Sh>(L, B);
+                if constexpr (bf16_shape<Sh>())
+                    if (!r) r = set_chain_lds_limits<Bf16Shape<Sh>>(L, B);
             }
             return r;
         });
@@ -2944,11 +3196,13 @@ bool bwd_xchg_coresident(int64_t nblk, size_t lds_bytes, int colocated)
 }
 
 int launch_bwd(const float *P, const Layout &L, int64_t B, const Workspace &ws, float *G, const int32_t *stop,
-               hipStream_t s, const FusedFwd *ff, const LossArgs *la, const BwdXchg *bxp)
+               hipStream_t s, const FusedFwd *ff, const LossArgs *la, const BwdXchg *bxp, int chain_nt)
 {
     const BwdShape sh0 = BwdShape::make(L, (int)B, rows_b(L, B));
     const unsigned nblk = (unsigned)(sh0.nA + sh0.nB + sh0.nC);
     const size_t lds = bwd_lds_bytes(L, B);
+    if (chain_nt == 0) chain_nt = bwd_chain_threads();
+    GS_REQUIRE(chain_nt == 256 || chain_nt == 512, "k_bwd_chain: %d threads (256 or 512)", chain_nt);
     BwdXchg bx{};
     if (bxp && bxp->world > 1) {
         GS_REQUIRE(bwd_xchg_fits(L, B), "k_bwd exchange: %u workgroups or their output slots exceed the limits",
@@ -2974,17 +3228,21 @@ int launch_bwd(const float *P, const Layout &L, int64_t B, const Workspace &ws, 
         auto chain = [&](auto shape) -> int {
             using S = decltype(shape);
             const float *fields = reinterpret_cast<const float *>(ff->fa);
-            const void *fn = ff->step_base ? (const void *)k_bwd_chain<S, true> : (const void *)k_bwd_chain<S, false>;
-            int rc = set_lds_limit(fn, lds);
-            if (rc) return rc;
-            if (ff->step_base)
-                hipLaunchKernelGGL((k_bwd_chain<S, true>), dim3(nblk), dim3(256), lds, s, P, ws.h1, ws.h2mask, ws.zpart,
-                                   fields, ws.x, (int)fstride, ff->k_local, t);
-            else
-                hipLaunchKernelGGL((k_bwd_chain<S, false>), dim3(nblk), dim3(256), lds, s, P, ws.h1, ws.h2mask,
+            auto go = [&](auto base, auto nt) -> int {
+                constexpr bool kBase = decltype(base)::value;
+                constexpr int kNT = decltype(nt)::value;
+                const size_t ldsc = bwd_lds_bytes(L, B, kNT);
+                int rc = set_lds_limit((const void *)k_bwd_chain<S, kBase, kNT>, ldsc);
+                if (rc) return rc;
+                hipLaunchKernelGGL((k_bwd_chain<S, kBase, kNT>), dim3(nblk), dim3(kNT), ldsc, s, P, ws.h1, ws.h2mask,
                                    ws.zpart, fields, ws.x, (int)fstride, ff->k_local, t);
-            GS_LAUNCH_CHECK("k_bwd_chain");
-            return GS_OK;
+                GS_LAUNCH_CHECK("k_bwd_chain");
+                return GS_OK;
+            };
+            using T8 = std::integral_constant<int, 512>;
+            using T4 = std::integral_constant<int, 256>;
+            if (ff->step_base) return chain_nt == 512 ? go(std::true_type{}, T8{}) : go(std::true_type{}, T4{});
+            return chain_nt == 512 ? go(std::false_type{}, T8{}) : go(std::false_type{}, T4{});
         };
         if (ff && la->bf16) {      // the bf16 mode (GS_HP_BF16)
             if constexpr (bf16_shape<Sh>()) {

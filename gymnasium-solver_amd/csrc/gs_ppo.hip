@@ -389,6 +389,7 @@ struct StepArgs {
     AdamArgs aa;
     bool sum_exchange;      // global mode: every rank's gradient is its share of the global mean (sum, no 1/world)
     bool act_stats;         // GS_HP_ACT_STATS (not in global mode): activation statistics into the records
+    int bwd_nt;             // k_bwd_chain's threads per workgroup (gs_ppo_update: GS_BWD_NT, read once per call; 0: per launch)
 };
 
 // glob != nullptr: gs_ppo_update_global's global-minibatch mode (include/gsamd.h)
@@ -496,7 +497,7 @@ int enqueue_step_fused(float *P, float *G, float *M, float *V, const Layout &L, 
     const bool inbwd = bwd_exchange_of(comm, L, B, &bx, sa.sum_exchange);
     int rc = launch_fwd_fused(P, L, B, ff, sa.la, ws, stop, s);
     if (rc) return rc;
-    rc = launch_bwd(P, L, B, ws, G, stop, s, &ff, &sa.la, inbwd ? &bx : nullptr);
+    rc = launch_bwd(P, L, B, ws, G, stop, s, &ff, &sa.la, inbwd ? &bx : nullptr, sa.bwd_nt);
     if (rc) return rc;
     if (!comm || inbwd) return launch_clip_adam(P, L, G, M, V, ws.part1, ws.sumsq, sa.aa, metrics, stop, s, false);
     return exchange_and_adam(P, G, M, V, L, sa, metrics, stop, ws, comm, s, &ff);
@@ -549,7 +550,7 @@ int enqueue_step_lagged(const ParamSet (&ps)[2], float *G, const Layout &L, cons
     af.aa = after ? exchanged_adam_args(sa_prev.aa, comm, sa_prev.sum_exchange) : sa_prev.aa;
     int rc = launch_fwd_fused(prev.P, L, B, ff, sa_prev.la, ws, stop, s, &af);
     if (rc) return rc;
-    rc = launch_bwd(cur.P, L, B, ws, G, stop, s, &ff, &sa_prev.la, inbwd ? &bx : nullptr);
+    rc = launch_bwd(cur.P, L, B, ws, G, stop, s, &ff, &sa_prev.la, inbwd ? &bx : nullptr, sa_prev.bwd_nt);
     if (rc || !after) return rc;
     int world = 1, n_slots = 0;
     rc = comm_grad_exchange(comm, G, L.P, Part1Fold{ws.part1, sa_prev.aa.nrb, L}, ws.sumsq, &n_slots, stop, s, &world);
@@ -806,6 +807,9 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
     // without a communicator; step 0's forward reads set 1, which starts as a copy of the
     // caller's parameters
     const bool lagged = fused && lagged_enabled() && has_lagged(L, batch);
+    // GS_BWD_NT=256 in the environment runs the single-GPU chain's backward with four waves per workgroup
+    // (the k_bwd body: bit-identical, slower on MI355X); a captured graph holds one of the two
+    const int bwd_nt = bwd_chain_threads();
     const ParamSet ps[2] = {{params, adam_m, adam_v}, {fw.p1, fw.m1, fw.v1}};
     if (lagged) GS_HIP(hipMemcpyAsync(fw.p1, params, sizeof(float) * (size_t)L.P, hipMemcpyDeviceToDevice, s));
     auto step_ff = [&](int64_t k_local, int64_t slot, const int64_t *base) {
@@ -819,11 +823,13 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
         StepArgs sp = make_step_args(hp, L, batch, adam_step0 + k > 0 ? adam_step0 + k : 1);   // step k-1's
         sp.aa.sched = sched;
         sp.aa.normsq = fw.normsq;      // the lagged forward indexes it by the applied step
+        sp.bwd_nt = bwd_nt;
         return enqueue_step_lagged(ps, grads, L, sp, batch, step_ff(k, k, base), k, metrics, stop_flag, ws, comm, st);
     };
     // the fused (non-lagged) chain's k_clip_adam of step k: its squared norm beside its record
     auto with_norm = [&](StepArgs a, int64_t k) {
         a.aa.normsq = fw.normsq ? fw.normsq + k : nullptr;
+        a.bwd_nt = bwd_nt;
         return a;
     };
     auto finish = [&]() -> int {
@@ -891,7 +897,7 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
     BwdXchg bx_key;
     const bool in_bwd = comm && bwd_exchange_of(comm, L, batch, &bx_key);
     key.n[4] = (int64_t)(intptr_t)stop_flag ^ ((int64_t)(intptr_t)comm << 1) ^ (fused ? 1 : 0) ^
-               ((int64_t)lagged << 62) ^ ((int64_t)in_bwd << 61);
+               ((int64_t)lagged << 62) ^ ((int64_t)in_bwd << 61) ^ ((int64_t)(fused && bwd_nt == 256) << 60);
     key.n[5] = ro.T * 1000003 + ro.N + (glob ? glob->batch_global << 40 : 0);
     uint32_t hbits[12];
     baked_hparam_bits(hp, hbits);

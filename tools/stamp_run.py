@@ -64,7 +64,10 @@ names = {0: ("k_fwd_chain<adam> (0,0)", ["loads landed (waitcnt: stamp build onl
          4: ("k_bwd roleB blk0", ["load slab", "dh2", "mfma dh1", "dW1 partial"]),
          5: ("k_bwd roleC blk0", ["load", "reduce + store"]),
          6: ("k_bwd roleB slab loads (wave 0, from role start)", ["landed"]),
-         7: ("k_bwd roleB loss rows (wave 3, from role start)", ["done"])}
+         7: ("k_bwd roleB loss rows (the last wave, from role start)", ["done"])}
+# eight-wave k_bwd_chain: thread 0 of roles A and C is a loss wave (the phases above); columns 13 / 14
+# of their slots are a loader wave (wave 4), from kernel entry
+LOADER = {2: ("h1 tile loads issued", "h1 tile in LDS"), 5: ("h2 tile loads issued", "h2 tile in LDS")}
 for k, (n, phases) in names.items():
     if cnt[k] == 0:
         continue
@@ -75,6 +78,9 @@ for k, (n, phases) in names.items():
         print(f"    {ph:24s} {per[i]:8.0f} cyc  {per[i] / 2.4e3:6.2f} us")
     if per[15] > 0:      # GS_STAMP_ENTRY: kernel entry -> first vector load issued (inside the first phase)
         print(f"    {'entry -> first vector load issued':24s} {per[15]:8.0f} cyc  {per[15] / 2.4e3:6.2f} us")
+    if k in LOADER and per[14] > 0:
+        for col, what in zip((13, 14), LOADER[k]):
+            print(f"    {'loader wave: entry -> ' + what:24s} {per[col]:8.0f} cyc  {per[col] / 2.4e3:6.2f} us")
 
 # chain timeline of the second update's first 2048 minibatches (100 MHz device clock -> us):
 # kernel spans from the first workgroup start to the last wave end, and the gaps between kernels
