@@ -16,6 +16,12 @@
 // The per-row head / loss / Adam arithmetic is gs_head.h's, shared with gs_mlp.hip.
 #include "gs_common.h"
 #include "gs_head.h"
+#include "gs_rollout1.h"
+#include "gs_tabular_env.h"
+#include "gs_cartpole_env.h"
+#include "gs_acrobot_env.h"
+#include "gs_mountaincar_env.h"
+#include "gs_bandit_env.h"
 
 namespace gs {
 
@@ -25,6 +31,7 @@ constexpr int kRows1 = 32;                      // rows of one tile of the updat
 constexpr int kMaxBatch1 = 1024;                // largest minibatch (mlp1_update checks it)
 constexpr size_t kLdsBudget1 = 160 * 1024;      // LDS of one CU (gfx950)
 constexpr int kRedDoubles = 3 * (256 + 16);     // block_reduce<3, double> scratch
+constexpr int kBlock1 = 8;                      // hidden units per block of the row forward (divides 16)
 
 __host__ __device__ constexpr int round4i(int n) { return (n + 3) & ~3; }
 
@@ -83,10 +90,52 @@ __device__ __forceinline__ int sample_row_checked(int s, int T, int N)
 }
 
 // ------------------------------------------------------------------------------------
-// k_act1: rollout step / value forward, one thread per env row, 256 rows per workgroup.
-// LDS (floats): Ps[round4(P)] xs[256][D | 1]
+// The forward of one row, shared by k_act1 and k_rollout1 so their chains cannot drift: Ps the
+// parameters in LDS (flat, Layout1's offsets), x the row's observation; z receives logits | value.
+// h_k = relu(b1[k] + sum_d W1[k][d] x[d]) as one fmaf chain in d order from the bias;
 // z[a] = bias + sum_k W[a][k] h[k] as one fmaf chain in k order: the update kernel forms the
 // same chain, so a replayed row's log-prob equals the update's under the same parameters.
+// ------------------------------------------------------------------------------------
+template <int AMAX>
+__device__ __forceinline__ void mlp1_forward_row(const float *Ps, const Layout1 &L, const float *x,
+                                                 float (&z)[AMAX + 1])
+{
+    const int D = L.D, H = L.H, A = L.A;
+    // Slots past the value head (a > A) run the value head's chain again and are never read: with
+    // no condition inside the loops the head reads are plain loads the compiler batches, where a
+    // guarded read became a branch per (k, a) and every fmaf waited for its own LDS round trip.
+    int hr[AMAX + 1];
+#pragma unroll
+    for (int a = 0; a < AMAX + 1; ++a) {
+        const int ac = a < A ? a : A;
+        hr[a] = L.head_row(ac);
+        z[a] = Ps[L.head_bias(ac)];
+    }
+    // kBlock1 hidden units at a time (H is a multiple of 16): their h chains are independent, so
+    // the LDS reads of a block are issued together and the row waits for a read's latency once per
+    // block, not once per fmaf; each h chain keeps its d order and each z[a] its k order
+    for (int k0 = 0; k0 < H; k0 += kBlock1) {
+        float h[kBlock1];
+#pragma unroll
+        for (int j = 0; j < kBlock1; ++j) h[j] = Ps[L.ob1 + k0 + j];
+#pragma unroll 4
+        for (int d = 0; d < D; ++d) {
+            const float xd = x[d];
+#pragma unroll
+            for (int j = 0; j < kBlock1; ++j) h[j] = fmaf(Ps[L.oW1 + (k0 + j) * D + d], xd, h[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kBlock1; ++j) {
+            const float hj = h[j] > 0.0f ? h[j] : 0.0f;
+#pragma unroll
+            for (int a = 0; a < AMAX + 1; ++a) z[a] = fmaf(Ps[hr[a] + k0 + j], hj, z[a]);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// k_act1: rollout step / value forward, one thread per env row, 256 rows per workgroup.
+// LDS (floats): Ps[round4(P)] xs[256][D | 1]
 // ------------------------------------------------------------------------------------
 template <int AMAX>
 __global__ __launch_bounds__(256) void k_act1(const float *__restrict__ P, Layout1 L, const float *__restrict__ obs,
@@ -98,7 +147,7 @@ __global__ __launch_bounds__(256) void k_act1(const float *__restrict__ P, Layou
     extern __shared__ float lds_f[];
     float *Ps = lds_f;
     float *xs = Ps + round4i(L.P);
-    const int tid = threadIdx.x, D = L.D, Dp = D | 1, H = L.H, A = L.A, A1 = A + 1;
+    const int tid = threadIdx.x, D = L.D, Dp = D | 1, A = L.A;
     const int64_t row0 = (int64_t)blockIdx.x * 256;
     const int nr = (int)(N - row0 < 256 ? N - row0 : 256);
     for (int p = tid; p < L.P; p += 256) Ps[p] = P[p];
@@ -110,22 +159,71 @@ __global__ __launch_bounds__(256) void k_act1(const float *__restrict__ P, Layou
     }
     __syncthreads();
     if (tid >= nr) return;
-    const float *x = xs + tid * Dp;
     float z[AMAX + 1];
-#pragma unroll
-    for (int a = 0; a < AMAX + 1; ++a) z[a] = a < A1 ? Ps[L.head_bias(a)] : 0.0f;
-    for (int k = 0; k < H; ++k) {
-        float h = Ps[L.ob1 + k];
-        for (int d = 0; d < D; ++d) h = fmaf(Ps[L.oW1 + k * D + d], x[d], h);
-        h = h > 0.0f ? h : 0.0f;
-#pragma unroll
-        for (int a = 0; a < AMAX + 1; ++a)
-            if (a < A1) z[a] = fmaf(Ps[L.head_row(a) + k], h, z[a]);
-    }
+    mlp1_forward_row<AMAX>(Ps, L, xs + tid * Dp, z);
     const int64_t r = row0 + tid;
     const uint64_t ctr = counter + (clock && mode == 0 ? clock[0] : 0ull);   // rollout clock (graph replay)
     head_act_row<AMAX>(z, A, mode, seed, ctr, r, actions ? actions + r : nullptr, logp ? logp + r : nullptr,
                        value ? value + r : nullptr);
+}
+
+// ------------------------------------------------------------------------------------
+// k_rollout1: a whole rollout of a device env in one launch, generic over the env type E
+// (gs_env_episode.h).  One thread owns one env for all T vector steps: the parameters sit in LDS,
+// the env's state in the thread's registers, its observation in the thread's own LDS row, so the
+// step loop has no barrier and no cross-thread arithmetic.  A workgroup is one wave
+// (kRollout1Envs envs): a few dozen envs then spread over as many CUs as they can, and the result
+// does not depend on the split.  The forward is k_act1's (mlp1_forward_row), the head
+// head_act_row with counter0 + t and the env's row id, the env step E::step: every row, the env's
+// tensors and the episode counters equal T rounds of k_act1 + k_env_step<E> bit for bit.
+// LDS (floats): Ps[round4(P)] xs[kRollout1Envs][D | 1]
+// ------------------------------------------------------------------------------------
+template <int AMAX, class E>
+__global__ __launch_bounds__(kRollout1Envs) void k_rollout1(const float *__restrict__ P, Layout1 L, int64_t N, int T,
+                                                            int mode, uint64_t rng_seed, uint64_t counter0,
+                                                            typename E::Args ev, RolloutRows rw)
+{
+    extern __shared__ float lds_f[];
+    float *Ps = lds_f;
+    float *xs = Ps + round4i(L.P);
+    const int tid = threadIdx.x, D = L.D, Dp = D | 1, A = L.A;
+    const int64_t me = (int64_t)blockIdx.x * kRollout1Envs + tid;
+    const bool live = me < N;
+    float *x = xs + tid * Dp;       // this env's observation: nobody else reads or writes the row
+    // ---- prologue: the parameters into LDS once, the env into registers, its observation into the row
+    for (int p = tid; p < L.P; p += kRollout1Envs) Ps[p] = P[p];
+    E env{};
+    if (live) {
+        env.load(ev, me);
+        for (int d = 0; d < D; ++d) x[d] = ev.obs[me * D + d];
+    }
+    __syncthreads();                // the parameters, staged by every lane
+    if (!live) return;
+    // replay reads the pre-filled action rows, one step ahead of its use
+    int64_t action = mode == 2 && T > 0 ? rw.actions[me] : 0;
+    for (int t = 0; t < T; ++t) {
+        const int64_t o = (int64_t)t * N + me;
+        float z[AMAX + 1];
+        mlp1_forward_row<AMAX>(Ps, L, x, z);
+        float logp, value;
+        head_act_row<AMAX>(z, A, mode, rng_seed, counter0 + (uint64_t)t, me, &action, &logp, &value);
+        const EnvStepOut so = env.step(ev, me, action);
+        const int64_t taken = action;
+        if (mode == 2 && t + 1 < T) action = rw.actions[o + N];
+        // the step's rows behind the env's own loads, so no load of a step waits for its stores;
+        // x is still the observation the action was taken on
+        for (int d = 0; d < D; ++d) rw.obs[o * D + d] = x[d];
+        if (mode != 2) rw.actions[o] = taken;
+        rw.logp[o] = logp;
+        rw.value[o] = value;
+        rw.reward[o] = so.reward;
+        rw.done[o] = so.done ? 1 : 0;
+        rw.timeout[o] = so.timeout ? 1 : 0;
+        env.write_obs(ev, x);
+    }
+    // ---- epilogue: the env's tensors and its observation back
+    env.store(ev, me);
+    for (int d = 0; d < D; ++d) ev.obs[me * D + d] = x[d];
 }
 
 // ------------------------------------------------------------------------------------
@@ -494,6 +592,60 @@ int mlp1_policy_act(const float *params, const gs_mlp_dims &d, const float *obs,
     });
 }
 
+size_t mlp1_rollout_lds_bytes(const gs_mlp_dims &d)
+{
+    const Layout1 L = Layout1::make(d.obs_dim, d.hidden1, d.n_actions);
+    return sizeof(float) * ((size_t)round4i(L.P) + (size_t)kRollout1Envs * (size_t)(L.D | 1));
+}
+
+bool mlp1_rollout_fits(const gs_mlp_dims &d) { return mlp1_rollout_lds_bytes(d) <= kLdsBudget1; }
+
+int mlp1_check_rollout_entry(const char *who, const gs_mlp_dims &dims, int64_t N, int64_t T, int mode,
+                             const float *params, const EnvArgs &ev, const RolloutRows &rw)
+{
+    GS_REQUIRE(dims.hidden2 == 0, "%s: serves a policy with one hidden layer (hidden2 == 0), got hidden2 = %d", who,
+               dims.hidden2);
+    int rc = mlp1_check_dims(dims);
+    if (rc) return rc;
+    GS_REQUIRE(N > 0 && (N + kRollout1Envs - 1) / kRollout1Envs < (int64_t)1 << 31 && T >= 0 && T < (int64_t)1 << 31,
+               "%s: bad N / T", who);
+    GS_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d not in {0,1,2}", who, mode);
+    GS_REQUIRE(ev.max_steps > 0, "%s: max_steps must be > 0", who);
+    GS_REQUIRE(params && ev.meta && ev.ep_ret && ev.obs && rw.obs && rw.actions && rw.logp && rw.value &&
+                   rw.reward && rw.done && rw.timeout,
+               "%s: null buffer", who);
+    return GS_OK;
+}
+
+template <class E>
+int mlp1_launch_rollout(const float *P, const gs_mlp_dims &d, int64_t N, int T, int mode, uint64_t rng_seed,
+                        uint64_t counter0, const typename E::Args &ev, const RolloutRows &rw, hipStream_t s)
+{
+    const Layout1 L = Layout1::make(d.obs_dim, d.hidden1, d.n_actions);
+    const size_t lds = mlp1_rollout_lds_bytes(d);
+    GS_REQUIRE(lds <= kLdsBudget1, "one-hidden-layer rollout: %zu bytes of LDS do not fit", lds);
+    const unsigned nb = (unsigned)((N + kRollout1Envs - 1) / kRollout1Envs);
+    return with_amax(L.A, [&](auto amax) {
+        constexpr int AMAX = decltype(amax)::value;
+        const int rl = set_lds_limit((const void *)k_rollout1<AMAX, E>, lds);
+        if (rl) return rl;
+        hipLaunchKernelGGL((k_rollout1<AMAX, E>), dim3(nb), dim3(kRollout1Envs), lds, s, P, L, N, T, mode, rng_seed,
+                           counter0, ev, rw);
+        GS_LAUNCH_CHECK("k_rollout1");
+        return (int)GS_OK;
+    });
+}
+#define GS_ROLLOUT1_INSTANCE(E)                                                                                 \
+    template int mlp1_launch_rollout<E>(const float *, const gs_mlp_dims &, int64_t, int, int, uint64_t, uint64_t, \
+                                        const E::Args &, const RolloutRows &, hipStream_t)
+GS_ROLLOUT1_INSTANCE(TabularEnv);
+GS_ROLLOUT1_INSTANCE(CartPoleEnv);
+GS_ROLLOUT1_INSTANCE(CartPoleShapedEnv);
+GS_ROLLOUT1_INSTANCE(AcrobotEnv);
+GS_ROLLOUT1_INSTANCE(MountainCarEnv);
+GS_ROLLOUT1_INSTANCE(BanditEnv);
+#undef GS_ROLLOUT1_INSTANCE
+
 int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const gs_mlp_dims &d,
                 const gs_ppo_hparams &hp, const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n,
                 int64_t adam_step0, float *metrics, int32_t *stop_flag, bool loss_only, hipStream_t s)
@@ -571,3 +723,101 @@ int mlp1_activation_stats(const float *params, const gs_mlp_dims &d, const gs_ro
 }
 
 }  // namespace gs
+
+using namespace gs;
+
+// ---- the gs_rollout1_* entries (include/gsamd.h) of the envs with their own tensors in the
+// argument list; gs_rollout1_tabular is in gs_tabular.hip beside the spec check it shares
+extern "C" int gs_rollout1_supported(gs_mlp_dims dims, int *supported)
+{
+    GS_REQUIRE(supported, "gs_rollout1_supported: null output");
+    *supported = 0;
+    GS_REQUIRE(dims.hidden2 == 0, "gs_rollout1_supported: serves a policy with one hidden layer (hidden2 == 0), got "
+                                  "hidden2 = %d", dims.hidden2);
+    int rc = mlp1_check_dims(dims);
+    if (rc) return rc;
+    *supported = mlp1_rollout_fits(dims) ? 1 : 0;
+    return GS_OK;
+}
+
+extern "C" int gs_rollout1_env(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                               uint64_t rng_seed, uint64_t rng_counter0, int kind, double *env_state,
+                               int32_t *env_meta, float *env_ep_ret, float *env_obs, int32_t max_steps,
+                               uint64_t env_seed, int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum,
+                               float *ep_len_sum, float *obs_rows, int64_t *action_rows, float *logp_rows,
+                               float *value_rows, float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows,
+                               void *stream)
+{
+    GS_REQUIRE(kind != GS_ENV_MOUNTAINCAR,
+               "gs_rollout1_env: MountainCar takes its count tables and wrappers through gs_rollout1_mountaincar");
+    GS_REQUIRE(kind != GS_ENV_BANDIT, "gs_rollout1_env: the bandit takes its spec through gs_rollout1_bandit");
+    GS_REQUIRE(kind == GS_ENV_CARTPOLE || kind == GS_ENV_ACROBOT, "gs_rollout1_env: env kind %d has no dynamics here",
+               kind);
+    const DynEnvArgs ev{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps, env_seed,
+                         env_offset},
+                        env_state};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    const char *bad = env_state ? nullptr : "null buffer";
+    if (kind == GS_ENV_CARTPOLE)
+        return rollout1_entry<CartPoleEnv>("gs_rollout1_env", params, dims, N, T, mode, rng_seed, rng_counter0, ev, rw,
+                                           CartPoleEnv::kObsDim, CartPoleEnv::kActions, bad, stream);
+    return rollout1_entry<AcrobotEnv>("gs_rollout1_env", params, dims, N, T, mode, rng_seed, rng_counter0, ev, rw,
+                                      AcrobotEnv::kObsDim, AcrobotEnv::kActions, bad, stream);
+}
+
+extern "C" int gs_rollout1_mountaincar(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                       uint64_t rng_seed, uint64_t rng_counter0, double *env_state,
+                                       int32_t *env_meta, float *env_ep_ret, float *env_obs, int32_t *env_counts,
+                                       gs_mountaincar_wrappers wrappers, int32_t max_steps, uint64_t env_seed,
+                                       int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum,
+                                       float *ep_len_sum, float *obs_rows, int64_t *action_rows, float *logp_rows,
+                                       float *value_rows, float *reward_rows, uint8_t *done_rows,
+                                       uint8_t *timeout_rows, void *stream)
+{
+    const MountainCarEnv::Args ev{{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
+                                    env_seed, env_offset},
+                                   env_state},
+                                  env_counts,
+                                  wrappers};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    const char *bad = env_state ? mountaincar_wrappers_error(wrappers, env_counts) : "null buffer";
+    return rollout1_entry<MountainCarEnv>("gs_rollout1_mountaincar", params, dims, N, T, mode, rng_seed, rng_counter0,
+                                          ev, rw, MountainCarEnv::kObsDim, MountainCarEnv::kActions, bad, stream);
+}
+
+extern "C" int gs_rollout1_cartpole_shaped(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                           uint64_t rng_seed, uint64_t rng_counter0, double *env_state,
+                                           double *env_prev_phi, int32_t *env_meta, float *env_ep_ret,
+                                           float *env_obs, gs_cartpole_wrappers wrappers, int32_t max_steps,
+                                           uint64_t env_seed, int64_t env_offset, int32_t *ep_done_count,
+                                           float *ep_ret_sum, float *ep_len_sum, float *obs_rows,
+                                           int64_t *action_rows, float *logp_rows, float *value_rows,
+                                           float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows,
+                                           void *stream)
+{
+    const CartPoleShapedEnv::Args ev{{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum,
+                                       max_steps, env_seed, env_offset},
+                                      env_state},
+                                     env_prev_phi,
+                                     wrappers};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return rollout1_entry<CartPoleShapedEnv>("gs_rollout1_cartpole_shaped", params, dims, N, T, mode, rng_seed,
+                                             rng_counter0, ev, rw, CartPoleShapedEnv::kObsDim,
+                                             CartPoleShapedEnv::kActions,
+                                             env_state && env_prev_phi ? nullptr : "null buffer", stream);
+}
+
+extern "C" int gs_rollout1_bandit(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                  uint64_t rng_seed, uint64_t rng_counter0, int32_t *env_meta, float *env_ep_ret,
+                                  float *env_obs, gs_bandit_spec spec, int32_t max_steps, uint64_t env_seed,
+                                  int64_t env_offset, int32_t *ep_done_count, float *ep_ret_sum, float *ep_len_sum,
+                                  float *obs_rows, int64_t *action_rows, float *logp_rows, float *value_rows,
+                                  float *reward_rows, uint8_t *done_rows, uint8_t *timeout_rows, void *stream)
+{
+    const BanditEnv::Args ev{{env_meta, env_ep_ret, env_obs, ep_done_count, ep_ret_sum, ep_len_sum, max_steps,
+                              env_seed, env_offset},
+                             spec};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    return rollout1_entry<BanditEnv>("gs_rollout1_bandit", params, dims, N, T, mode, rng_seed, rng_counter0, ev, rw,
+                                     spec.n_arms, spec.n_arms, bandit_spec_error(spec), stream);
+}

@@ -8,6 +8,7 @@
 // type is in gs_tabular_env.h, the kernels in gs_env_kernels.h.  The numpy twin is
 // tests/tabular_twin.py.
 #include "gs_env_kernels.h"
+#include "gs_rollout1.h"
 #include "gs_tabular_env.h"
 
 namespace {
@@ -66,4 +67,26 @@ extern "C" int gs_tabular_step(int32_t *state_dev, int32_t *meta_dev, float *ep_
                                max_steps, seed, env_offset},
                               state_dev, spec, next_dev, reward_dev, term_dev, starts_dev};
     return launch_env_step<TabularEnv>(ev, actions_dev, N, rewards_row_dev, dones_row_dev, timeouts_row_dev, stream);
+}
+
+// The whole rollout of a one-hidden-layer policy on the tabular env in one launch (gs_mlp1.hip
+// k_rollout1<AMAX, TabularEnv>): gs_tabular_step's spec / table checks, then gs_rollout1.h's.
+extern "C" int gs_rollout1_tabular(const float *params, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                   uint64_t rng_seed, uint64_t rng_counter0, int32_t *state_dev, int32_t *meta_dev,
+                                   float *ep_ret_dev, float *obs_dev, gs_tabular_spec spec, const int32_t *next_dev,
+                                   const float *reward_dev, const uint8_t *term_dev, const int32_t *starts_dev,
+                                   int32_t max_steps, uint64_t seed, int64_t env_offset, int32_t *ep_done_count_dev,
+                                   float *ep_ret_sum_dev, float *ep_len_sum_dev, float *obs_rows, int64_t *action_rows,
+                                   float *logp_rows, float *value_rows, float *reward_rows, uint8_t *done_rows,
+                                   uint8_t *timeout_rows, void *stream)
+{
+    int rc = check_spec(spec, "gs_rollout1_tabular");
+    if (rc) return rc;
+    const TabularEnv::Args ev{{meta_dev, ep_ret_dev, obs_dev, ep_done_count_dev, ep_ret_sum_dev, ep_len_sum_dev,
+                               max_steps, seed, env_offset},
+                              state_dev, spec, next_dev, reward_dev, term_dev, starts_dev};
+    const RolloutRows rw{obs_rows, action_rows, logp_rows, value_rows, reward_rows, done_rows, timeout_rows};
+    const char *bad = !state_dev ? "null buffer" : (next_dev && reward_dev && term_dev && starts_dev ? nullptr : "null table");
+    return rollout1_entry<TabularEnv>("gs_rollout1_tabular", params, dims, N, T, mode, rng_seed, rng_counter0, ev, rw,
+                                      spec.obs_dim, spec.n_actions, bad, stream);
 }

@@ -1,9 +1,11 @@
 // gs_tabular_env.h — the generic tabular device env: the env type TabularEnv behind the step
-// kernels (gs_tabular.hip), see gs_env_episode.h.  Any finite MDP whose outcomes per (state,
+// kernels (gs_tabular.hip) and the one-hidden-layer policy's one-launch rollout (gs_mlp1.hip
+// k_rollout1, entry gs_rollout1_tabular), see gs_env_episode.h.  Any finite MDP whose outcomes per (state,
 // action) are K equiprobable alternatives, given as three read-only tables in HBM (next state,
 // reward, terminated; [S][A][K]).  The observation is the reference's
-// gym_wrappers/discrete_encoder.py applied on the env's own thread, as float32.  It has no
-// one-launch rollout.  Twin: tests/tabular_twin.py.
+// gym_wrappers/discrete_encoder.py applied on the env's own thread, as float32.  The
+// two-hidden-layer one-launch rollout (gs_mlp.hip k_rollout_env) does not serve it.
+// Twin: tests/tabular_twin.py.
 #pragma once
 
 #include "gs_env_episode.h"

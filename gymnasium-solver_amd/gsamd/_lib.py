@@ -207,6 +207,21 @@ def _load():
         "gs_tabular_reset": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, i64, u64, i64, vp]),
         "gs_tabular_step": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp,
                                            vp, vp, vp, vp, vp]),
+        # the one-hidden-layer policy's one-launch rollouts: their two-hidden-layer siblings' lists
+        "gs_rollout1_supported": (ctypes.c_int, [MlpDims, vp]),
+        "gs_rollout1_env": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, ctypes.c_int, vp, vp, vp, vp,
+                                           i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_rollout1_cartpole_shaped": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp,
+                                                       vp, CartPoleWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp,
+                                                       vp, vp, vp, vp, vp]),
+        "gs_rollout1_mountaincar": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
+                                                   MountainCarWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                   vp, vp, vp]),
+        "gs_rollout1_bandit": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, BanditSpec,
+                                              i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs_rollout1_tabular": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp,
+                                               TabularSpec, vp, vp, vp, vp, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp,
+                                               vp, vp, vp, vp]),
         "gs_atari_preprocess": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),
         "gs_atari_render": (ctypes.c_int, [vp, i64, u64, i64, u64, vp]),
         "gs_atari_env_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, u64, i64, vp]),
@@ -253,7 +268,9 @@ EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_norma
             "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",
             "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar",
             "gs_cartpole_shaped_reset", "gs_cartpole_shaped_step", "gs_rollout_cartpole_shaped", "gs_bandit_reset",
-            "gs_bandit_step", "gs_rollout_bandit", "gs_tabular_reset", "gs_tabular_step", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
+            "gs_bandit_step", "gs_rollout_bandit", "gs_tabular_reset", "gs_tabular_step",
+            "gs_rollout1_supported", "gs_rollout1_env", "gs_rollout1_cartpole_shaped", "gs_rollout1_mountaincar",
+            "gs_rollout1_bandit", "gs_rollout1_tabular", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
             "gs_comm_init", "gs_comm_xgmi_create", "gs_comm_xgmi_connect", "gs_comm_status", "gs_comm_error_record",
             "gs_comm_xgmi_set_colocation", "gs_comm_xgmi_set_bwd_exchange", "gs_comm_xgmi_reset",
             "gs_comm_allreduce_mean_f32", "gs_comm_allreduce_sum_f64", "gs_ppo_global_adv_stats",

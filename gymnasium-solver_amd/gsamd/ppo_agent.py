@@ -56,13 +56,15 @@ class MinibatchIndices:
 class DevicePPOAgent:
     def __init__(self, config, env=None, device: Optional[str] = None, rank: int = 0, world_size: int = 1,
                  comm=None, use_graph: bool = True, track_stats: bool = True, one_launch: bool = True,
-                 env_factory=None):
+                 env_factory=None, one_launch_mlp1: bool = False):
         self.config = config
         self.env_factory = env_factory       # stage -> host VectorEnv (configs without device dynamics)
         self.device = torch.device(device or f"cuda:{torch.cuda.current_device()}")
         self.rank, self.world_size, self.comm = int(rank), int(world_size), comm
         self.use_graph = bool(use_graph)
         self.one_launch = bool(one_launch)      # device env + LDS-sized MLP: one-launch rollouts
+        # opt-in: one-launch rollouts for a one-hidden-layer policy too (every stage's collector)
+        self.one_launch_mlp1 = bool(one_launch_mlp1)
         self.track_stats = bool(track_stats)
         # schedulable hyper-parameters (base_agent.py:72-77)
         self.policy_lr = config.policy_lr
@@ -221,7 +223,8 @@ class DevicePPOAgent:
         self._rollout_collectors[stage] = DeviceRolloutCollector(
             self.get_env(stage), self.policy_model, c.n_steps, gamma=c.gamma, gae_lambda=c.gae_lambda,
             rng_seed=c.seed + 7919 * self.rank, track_stats=self.track_stats, use_graph=self.use_graph,
-            one_launch=self.one_launch, normalize_advantages=self._rollout_adv_norm())
+            one_launch=self.one_launch, normalize_advantages=self._rollout_adv_norm(),
+            one_launch_mlp1=self.one_launch_mlp1)
 
     def _rollout_adv_norm(self) -> bool:
         """normalize_advantages == "rollout": the collector normalises each rollout's advantages
@@ -238,7 +241,7 @@ class DevicePPOAgent:
             self._rollout_collectors[stage] = DeviceRolloutCollector(
                 env, self.policy_model, c.n_steps, gamma=c.gamma, gae_lambda=c.gae_lambda,
                 rng_seed=c.seed + 1000 + 7919 * self.rank, track_stats=True,
-                normalize_advantages=self._rollout_adv_norm())
+                normalize_advantages=self._rollout_adv_norm(), one_launch_mlp1=self.one_launch_mlp1)
         return self._rollout_collectors[stage]
 
     # ---- checkpoints (agents/base_agent.py:658-885) -----------------------------------------
@@ -832,7 +835,8 @@ def build_agent(config, *args, **kwargs):
     FrozenLake-v1 and Taxi-v3 (with their DiscreteEncoder) on the device tabular env; any other env_id
     needs env= / env_factory= (the host VectorEnv
     the reference's build_env_from_config returns); the synthetic env only with
-    env_dynamics='synthetic'."""
+    env_dynamics='synthetic'.  one_launch_mlp1=True (default False) lets a one-hidden-layer policy
+    (mlp_tiny) on a device env collect each rollout in one launch instead of replaying its step graph."""
     from .config import from_reference_config
     algo = getattr(getattr(config, "algo_id", None), "value", getattr(config, "algo_id", None))
     if algo == "reinforce":         # agents/reinforce: Monte Carlo targets + the large-batch policy-gradient update

@@ -174,6 +174,18 @@ class DeviceCartPoleVecEnv(DeviceVecEnv):
         check(lib.gs_rollout_env(*head, int(self.env_kind), ptr(self.state), ptr(self.meta), ptr(self.ep_ret),
                                  ptr(self.obs), *tail), "gs_rollout_env")
 
+    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
+        """rollout_into for a one-hidden-layer policy: the gs_rollout1_* entry of the same arguments."""
+        head = self._policy_args(pm, buf, mode, rng_seed, counter0)
+        tail = (self.max_steps, self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf))
+        if self.wrappers_c is not None:
+            check(lib.gs_rollout1_cartpole_shaped(*head, ptr(self.state), ptr(self.prev_phi), ptr(self.meta),
+                                                  ptr(self.ep_ret), ptr(self.obs), self.wrappers_c, *tail),
+                  "gs_rollout1_cartpole_shaped")
+            return
+        check(lib.gs_rollout1_env(*head, int(self.env_kind), ptr(self.state), ptr(self.meta), ptr(self.ep_ret),
+                                  ptr(self.obs), *tail), "gs_rollout1_env")
+
 
 class DeviceAcrobotVecEnv(DeviceVecEnv):
     """Acrobot-v1 on device (gymnasium 1.x "book" dynamics restated in
@@ -208,6 +220,13 @@ class DeviceAcrobotVecEnv(DeviceVecEnv):
                                  ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.max_steps,
                                  self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf)),
               "gs_rollout_env")
+
+    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
+        """rollout_into for a one-hidden-layer policy."""
+        check(lib.gs_rollout1_env(*self._policy_args(pm, buf, mode, rng_seed, counter0), int(self.env_kind),
+                                  ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.max_steps,
+                                  self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf)),
+              "gs_rollout1_env")
 
 
 def mountaincar_wrappers_struct(wrappers) -> MountainCarWrappers:
@@ -283,6 +302,13 @@ class DeviceMountainCarVecEnv(DeviceVecEnv):
                                          self.wrappers_c, self.max_steps, self.seed, self.env_offset,
                                          *self._episode_counters(), *self._row_args(buf)), "gs_rollout_mountaincar")
 
+    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
+        """rollout_into for a one-hidden-layer policy."""
+        check(lib.gs_rollout1_mountaincar(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
+                                          ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self._counts_ptr(),
+                                          self.wrappers_c, self.max_steps, self.seed, self.env_offset,
+                                          *self._episode_counters(), *self._row_args(buf)), "gs_rollout1_mountaincar")
+
 
 class DeviceBanditVecEnv(DeviceVecEnv):
     """Bandit-v0 on device (csrc/gs_bandit_env.h restates the reference's
@@ -336,6 +362,13 @@ class DeviceBanditVecEnv(DeviceVecEnv):
                                     self.env_offset, *self._episode_counters(), *self._row_args(buf)),
               "gs_rollout_bandit")
 
+    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
+        """rollout_into for a one-hidden-layer policy (any n_arms the env takes)."""
+        check(lib.gs_rollout1_bandit(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.meta),
+                                     ptr(self.ep_ret), ptr(self.obs), self.spec, self.max_steps, self.seed,
+                                     self.env_offset, *self._episode_counters(), *self._row_args(buf)),
+              "gs_rollout1_bandit")
+
 
 class DeviceTabularVecEnv(DeviceVecEnv):
     """A tabular env on device (csrc/gs_tabular.hip): FrozenLake-v1 (`kind` "frozenlake", 4x4 or
@@ -343,9 +376,11 @@ class DeviceTabularVecEnv(DeviceVecEnv):
     term, starts, n_states, n_actions, K) passed as `tables`.  The observation is the reference's
     DiscreteEncoder (`encoding` array / binary / onehot) of the state, as float32.  NEXT_STEP
     autoreset, TimeLimit `max_steps` (default: the registered id's, 100 / 200).  The tables are
-    uploaded once, here.  No env_kind: a one-hidden-layer policy has no one-launch rollout, the
-    collector replays its step graph.  Parity with gymnasium's own episodes is unpinned (the
-    outcome and reset draws use the counter hash, not PCG64)."""
+    uploaded once, here.  No env_kind (the two-hidden-layer one-launch rollout does not serve it):
+    by default the collector replays its step graph; a one-hidden-layer policy's whole rollout is
+    one launch through rollout1_into when the collector is built with one_launch_mlp1=True.
+    Parity with gymnasium's own episodes is unpinned (the outcome and reset draws use the counter
+    hash, not PCG64)."""
 
     def __init__(self, n_envs, kind="frozenlake", encoding="binary", map_name="4x4", is_slippery=True, seed=42,
                  env_offset=0, max_steps=None, tables=None, device="cuda", **_):
@@ -382,6 +417,14 @@ class DeviceTabularVecEnv(DeviceVecEnv):
                                   ptr(self.starts), ptr(actions), self.num_envs, self.max_steps, self.seed,
                                   self.env_offset, ptr(rewards_row), ptr(dones_row), ptr(timeouts_row),
                                   *self._episode_counters(), stream_handle()), "gs_tabular_step")
+
+    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
+        """The whole rollout of a one-hidden-layer policy in one launch (gs_rollout1_tabular)."""
+        check(lib.gs_rollout1_tabular(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
+                                      ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
+                                      ptr(self.next_table), ptr(self.reward_table), ptr(self.term_table),
+                                      ptr(self.starts), self.max_steps, self.seed, self.env_offset,
+                                      *self._episode_counters(), *self._row_args(buf)), "gs_rollout1_tabular")
 
 
 class DeviceRolloutBuffer:
@@ -494,7 +537,8 @@ class DeviceRolloutCollector:
     def __init__(self, env, policy_model, n_steps, *, gamma: float = 0.99, gae_lambda: float = 0.95,
                  stats_window_size: int = 100, rng_seed: int = 42, track_stats: bool = True,
                  use_graph: bool = True, one_launch: bool = True, normalize_advantages: bool = False,
-                 returns_type: str = "gae:rtg", advantages_type: str = "gae", normalize_returns: bool = False, **kwargs):
+                 returns_type: str = "gae:rtg", advantages_type: str = "gae", normalize_returns: bool = False,
+                 one_launch_mlp1: bool = False, **kwargs):
         self.env = env
         self.policy_model = policy_model
         self.n_steps = int(n_steps)
@@ -527,6 +571,11 @@ class DeviceRolloutCollector:
         # env_kind; rows bit-identical to the step-wise loop)
         self.one_launch = bool(one_launch) and hasattr(policy_model, "dims") and \
             self._one_launch_supported(env, policy_model)
+        # opt-in: a one-hidden-layer policy on a device env with a rollout1_into runs the whole
+        # rollout as one launch too (gs_rollout1_*: one thread per env; rows bit-identical to the
+        # step-wise loop).  Off by default: such a policy then takes the step graph, as before.
+        self.one_launch_mlp1 = bool(one_launch_mlp1) and not self.one_launch and hasattr(policy_model, "dims") and \
+            self._one_launch_mlp1_supported(env, policy_model)
         self._graphs = {}
         self._clock = None
         self.total_rollouts = self.total_steps = self.total_vec_steps = self.total_episodes = 0
@@ -596,7 +645,7 @@ class DeviceRolloutCollector:
         mode = 2 if replay_actions is not None else (1 if deterministic else 0)
         native = getattr(self.env, "device_native", False)
         self.rollout_episodes = 0
-        if self.one_launch:
+        if self.one_launch or self.one_launch_mlp1:
             if replay_actions is not None:
                 buf.actions.copy_(replay_actions)
             self._collect_one_launch(mode)
@@ -665,10 +714,23 @@ class DeviceRolloutCollector:
         check(lib.gs_rollout_env_supported(pm.dims, int(kind), ctypes.byref(v)), "gs_rollout_env_supported")
         return bool(v.value)
 
+    @staticmethod
+    def _one_launch_mlp1_supported(env, pm) -> bool:
+        """A one-hidden-layer policy on a device env that has a rollout1_into, when
+        gs_rollout1_supported takes the shape."""
+        if int(getattr(pm.dims, "hidden2", -1)) != 0 or not getattr(env, "device_native", False) or \
+                not hasattr(env, "rollout1_into"):
+            return False
+        v = ctypes.c_int()
+        check(lib.gs_rollout1_supported(pm.dims, ctypes.byref(v)), "gs_rollout1_supported")
+        return bool(v.value)
+
     def _collect_one_launch(self, mode):
         """The T vector steps as one launch (policy act + env step per step, envs resident in
-        LDS): the env's own gs_rollout_* call (rollout_into)."""
-        self.env.rollout_into(self.policy_model, self._buffer, mode, self.rng_seed, self.total_vec_steps)
+        LDS): the env's own gs_rollout_* call (rollout_into), gs_rollout1_* (rollout1_into) for a
+        one-hidden-layer policy."""
+        run = self.env.rollout1_into if self.one_launch_mlp1 else self.env.rollout_into
+        run(self.policy_model, self._buffer, mode, self.rng_seed, self.total_vec_steps)
 
     def _steps_into_buffer(self, mode, clock=None):
         """The rollout's T vector steps on a device env: policy act (writes the step's obs /

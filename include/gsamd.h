@@ -101,7 +101,8 @@ int gs_sampler_stream_i32(int64_t data_len, int64_t num_passes, uint64_t seed, i
  * gs_ppo_update_workspace_bytes, gs_ppo_update, gs_ppo_minibatch_step, gs_ppo_loss and
  * gs_mlp_activation_stats, in fp32 on one GPU; GS_E_INVALID from gs_ppo_stage, gs_ppo_update_global,
  * gs_ppo_exchange_inside_bwd, gs_rollout_synth / _env / _mountaincar, with GS_HP_BF16 and with a
- * communicator; gs_rollout_synth_supported / gs_rollout_env_supported answer 0.
+ * communicator; gs_rollout_synth_supported / gs_rollout_env_supported answer 0.  Its one-launch
+ * rollouts on the device envs are entries of their own, gs_rollout1_* (below the tabular envs).
  * Its update (gs_ppo_update: every minibatch of the call in ONE launch of one 256-thread workgroup;
  * use_graph is accepted and ignored) keeps the parameters, both Adam moments and the gradient in
  * LDS, so the shape must satisfy, with P4 = P rounded up to 4 and A1 = A + 1:
@@ -734,6 +735,63 @@ int gs_tabular_step(int32_t *state_dev, int32_t *meta_dev, float *ep_ret_dev, fl
                     const int32_t *starts_dev, const int64_t *actions_dev, int64_t N, int32_t max_steps, uint64_t seed,
                     int64_t env_offset, float *rewards_row_dev, uint8_t *dones_row_dev, uint8_t *timeouts_row_dev,
                     int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, void *stream);
+
+/* ---------------------------------------------------------------- one-launch rollouts, one hidden layer
+ * A whole rollout of a device env in ONE launch for the one-hidden-layer policy (hidden2 == 0;
+ * csrc/gs_mlp1.hip k_rollout1): one thread owns one env for all T vector steps, the parameters in
+ * LDS, the env's state in registers, its observation in the thread's own LDS row; a workgroup is
+ * one wave of 64 envs and the result does not depend on that split.  The forward is
+ * gs_policy_act's one-hidden-layer arithmetic in its order, the env step the env's gs_*_step, so
+ * every row, the final env tensors and the episode counters equal T calls of gs_policy_act + the
+ * env's step bit for bit, in all three modes (mode 2 reads action_rows_dev) and for any N; the rng
+ * counter of step t is rng_counter0 + t and the row id the env's index.  These entries take
+ * hidden2 == 0 only (GS_E_INVALID otherwise; the gs_rollout_* entries above keep refusing it and
+ * gs_rollout_env_supported keeps answering 0), check what their two-hidden-layer siblings check,
+ * need dims to be the env's (obs dim and actions) and do nothing for T == 0.
+ * gs_rollout1_supported: *supported_host = 1 when dims lie in the one-hidden-layer envelope (beside
+ * gs_mlp_dims) and 4 (round4(P) + 64 (obs_dim | 1)) bytes fit in 160 KiB of LDS, 0 with GS_OK for
+ * a valid shape that does not fit, GS_E_INVALID for hidden2 != 0 or dims outside the envelope.
+ * gs_rollout1_env (kind GS_ENV_CARTPOLE / GS_ENV_ACROBOT), gs_rollout1_cartpole_shaped,
+ * gs_rollout1_mountaincar and gs_rollout1_bandit take the argument lists of gs_rollout_env,
+ * gs_rollout_cartpole_shaped, gs_rollout_mountaincar and gs_rollout_bandit unchanged (the bandit
+ * up to GS_BANDIT_MAX_ARMS arms).  gs_rollout1_tabular takes the tabular env's tensors, spec and
+ * tables as gs_tabular_step does (the same spec / table checks; dims.obs_dim == spec.obs_dim,
+ * dims.n_actions == spec.n_actions) between the policy arguments and the episode counters. */
+int gs_rollout1_supported(gs_mlp_dims dims, int *supported_host);
+int gs_rollout1_env(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
+                    uint64_t rng_counter0, int kind, double *env_state_dev, int32_t *env_meta_dev,
+                    float *env_ep_ret_dev, float *env_obs_dev, int32_t max_steps, uint64_t env_seed, int64_t env_offset,
+                    int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, float *obs_rows_dev,
+                    int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev, float *reward_rows_dev,
+                    uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
+int gs_rollout1_cartpole_shaped(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                                uint64_t rng_seed, uint64_t rng_counter0, double *env_state_dev,
+                                double *env_prev_phi_dev, int32_t *env_meta_dev, float *env_ep_ret_dev,
+                                float *env_obs_dev, gs_cartpole_wrappers wrappers, int32_t max_steps, uint64_t env_seed,
+                                int64_t env_offset, int32_t *ep_done_count_dev, float *ep_ret_sum_dev,
+                                float *ep_len_sum_dev, float *obs_rows_dev, int64_t *action_rows_dev,
+                                float *logp_rows_dev, float *value_rows_dev, float *reward_rows_dev,
+                                uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
+int gs_rollout1_mountaincar(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode,
+                            uint64_t rng_seed, uint64_t rng_counter0, double *env_state_dev, int32_t *env_meta_dev,
+                            float *env_ep_ret_dev, float *env_obs_dev, int32_t *env_counts_dev,
+                            gs_mountaincar_wrappers wrappers, int32_t max_steps, uint64_t env_seed, int64_t env_offset,
+                            int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev,
+                            float *obs_rows_dev, int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev,
+                            float *reward_rows_dev, uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
+int gs_rollout1_bandit(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
+                       uint64_t rng_counter0, int32_t *env_meta_dev, float *env_ep_ret_dev, float *env_obs_dev,
+                       gs_bandit_spec spec, int32_t max_steps, uint64_t env_seed, int64_t env_offset,
+                       int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev, float *obs_rows_dev,
+                       int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev, float *reward_rows_dev,
+                       uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
+int gs_rollout1_tabular(const float *params_dev, gs_mlp_dims dims, int64_t N, int64_t T, int mode, uint64_t rng_seed,
+                        uint64_t rng_counter0, int32_t *state_dev, int32_t *meta_dev, float *ep_ret_dev,
+                        float *obs_dev, gs_tabular_spec spec, const int32_t *next_dev, const float *reward_dev,
+                        const uint8_t *term_dev, const int32_t *starts_dev, int32_t max_steps, uint64_t seed,
+                        int64_t env_offset, int32_t *ep_done_count_dev, float *ep_ret_sum_dev, float *ep_len_sum_dev,
+                        float *obs_rows_dev, int64_t *action_rows_dev, float *logp_rows_dev, float *value_rows_dev,
+                        float *reward_rows_dev, uint8_t *done_rows_dev, uint8_t *timeout_rows_dev, void *stream);
 
 /* The fp32 MFMA GEMM under the CNN path (convolutions as GEMMs, fc, heads), exported for its
  * tests: row-major C[M][N] = op(A) op(B) + beta C (+ bias[n]) (ReLU if relu), op(X) = X^T
