@@ -331,6 +331,10 @@ int launch_loss(const float *P, const Layout &L, int64_t B, const Workspace &ws,
                 int32_t *stop, hipStream_t s);
 // nt: threads per workgroup (512: the single-GPU chain entry's eight waves keep more partial tiles)
 size_t bwd_lds_bytes(const Layout &L, int64_t B, int nt = 256);
+// k_bwd's static LDS (its block-reduction buffer; the fused bodies keep three) in floats, and the
+// workgroup's whole LDS, static + dynamic: what has to fit in the CU's 160 KB
+constexpr int bwd_sbuf_floats(bool fused) { return fused ? 3 * 272 : 272; }
+size_t bwd_lds_total_bytes(const Layout &L, int64_t B);
 int prepare_kernels(const Layout &L, int64_t B);
 // Threads per workgroup of the single-GPU chain entry k_bwd_chain: 512, or 256 with GS_BWD_NT=256 in
 // the environment (the same bits: the A/B arm and the tests' reference); gs_ppo_update reads it once

@@ -645,9 +645,9 @@ __device__ __forceinline__ void fwd_hidden_body(
         copy_to_lds(W1s, P + L.oW1, H1 * D);
         copy_to_lds(b1s, P + L.ob1, H1);
         if (tid < kTile) b2s[tid] = c0 + tid < H2 ? P[L.ob2 + c0 + tid] : 0.0f;
-        if (tid < A1 * kTile) {
-            const int a = tid >> 4, j = tid & 15;
-            whs[tid] = c0 + j < H2 ? P[L.head_row(a) + c0 + j] : 0.0f;
+        for (int u = tid; u < A1 * kTile; u += NT) {      // more than one pass from 16 actions on
+            const int a = u >> 4, j = u & 15;
+            whs[u] = c0 + j < H2 ? P[L.head_row(a) + c0 + j] : 0.0f;
         }
     }
     // W2 tile: with compile-time shapes the loads go to registers AFTER the h1 operands, so the
@@ -1584,6 +1584,14 @@ size_t bwd_lds_bytes(const Layout &L, int64_t B, int nt)
     return (size_t)m * sizeof(float);
 }
 
+// dynamic + static: the k_bwd entries keep sbuf beside the dynamic part (the fused bodies, which
+// run the compile-time shapes only, three of them)
+size_t bwd_lds_total_bytes(const Layout &L, int64_t B)
+{
+    const bool fused = has_fused(L, B);
+    return bwd_lds_bytes(L, B, fused ? 512 : 256) + sizeof(float) * bwd_sbuf_floats(fused);
+}
+
 // Fused path: the loss rows a workgroup needs (dLoss/dlogits | dLoss/dvalue) are computed
 // from the forward's partial heads straight into LDS, so the chain has no separate loss
 // launch.  Threads [t0, t0 + nthr) take rows [r0, r0 + n); dscr != nullptr also keeps the 14
@@ -1682,7 +1690,7 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
     if constexpr (FUSED && BASE) kstep += ff.step_base ? *ff.step_base : 0;
     if constexpr (FUSED) GS_SPAN_START(1, kstep)
     extern __shared__ float lds[];
-    __shared__ float sbuf[FUSED ? 3 * 272 : 272];    // fused: role C's {slot, policy, value} sums
+    __shared__ float sbuf[bwd_sbuf_floats(FUSED)];   // fused: role C's {slot, policy, value} sums
     const Layout L = S::lay(Lrt);
     const int B = S::batch(Brt);
     const int D = L.D, H1 = L.H1, H2 = L.H2, A = L.A, A1 = A + 1;
@@ -1820,9 +1828,9 @@ __device__ __forceinline__ void bwd_body(const float *__restrict__ P, const Layo
                 loss_rows_lds<S>(P, L, zpart, ff, la, B, kstep, 0, B, dzs, nullptr);
             else
                 copy_to_lds(dzs, dz, B * A1);
-            if (tid < A1 * kTile) {
-                const int a = tid >> 4, j = tid & 15;
-                whs[tid] = n0 + j < H2 ? P[L.head_row(a) + n0 + j] : 0.0f;
+            for (int u = tid; u < A1 * kTile; u += 256) {     // more than one pass from 16 actions on
+                const int a = u >> 4, j = u & 15;
+                whs[u] = n0 + j < H2 ? P[L.head_row(a) + n0 + j] : 0.0f;
             }
             for (int b = tid; b < Bp; b += 256) mkA[b] = b < B ? (int)h2mask[(int64_t)b * sh.ncb + nb] : 0;
             const int q4 = kw / 4;

@@ -568,7 +568,8 @@ int validate_update(const gs_mlp_dims &dims, const gs_rollout_view &ro, int64_t 
                "rollout view has a null buffer");
     GS_REQUIRE(ws, "null workspace");
     const Layout L = layout_of(dims);
-    GS_REQUIRE(bwd_lds_bytes(L, batch) <= 160 * 1024, "batch %lld too large for the LDS budget", (long long)batch);
+    GS_REQUIRE(bwd_lds_total_bytes(L, batch) <= 160 * 1024, "batch %lld too large for the LDS budget: %zu bytes",
+               (long long)batch, bwd_lds_total_bytes(L, batch));
     GS_REQUIRE(fwd_lds_bytes(L) <= 160 * 1024, "obs_dim x hidden1 too large for the LDS budget");
     GS_REQUIRE(ro.T * ro.N < (int64_t)1 << 31, "rollout larger than 2^31 samples");
     return GS_OK;
