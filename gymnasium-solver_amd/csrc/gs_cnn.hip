@@ -29,6 +29,8 @@
 #include "gs_conv.h"
 #include "gs_fields.h"
 #include "gs_gemm.h"
+#include "gs_head.h"
+#include "gs_hparams.h"
 
 namespace gs {
 
@@ -399,14 +401,6 @@ __device__ __forceinline__ MRow mrow_stats(const float (&z)[AM + 1], const CnnLa
     return h;
 }
 
-__device__ __forceinline__ uint64_t mix64d(uint64_t x)
-{
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-
 // ---- rollout: action select over the valid set, log_prob, value of row r from its head outputs
 // zr (biases added; zr[A] = the value)
 template <int AM>
@@ -432,7 +426,7 @@ __device__ __forceinline__ void act_select(const float (&zr)[AM + 1], float v, i
         actions[r] = act;
     } else {
         const uint64_t ctr = counter + (clock ? clock[0] : 0ull);   // rollout clock (graph replay)
-        const uint64_t hh = mix64d(mix64d(mix64d(seed) ^ ctr) ^ (uint64_t)r);
+        const uint64_t hh = mix64(mix64(mix64(seed) ^ ctr) ^ (uint64_t)r);
         const float u = (float)(hh >> 40) * (1.0f / 16777216.0f);
         float c = 0.f;
         int last = 0;
@@ -510,7 +504,7 @@ __device__ __forceinline__ void act_select_wave(const float *__restrict__ zsum, 
             actions[r] = act;
         } else {
             const uint64_t ctr = counter + (clock ? clock[0] : 0ull);   // rollout clock (graph replay)
-            const uint64_t hh = mix64d(mix64d(mix64d(seed) ^ ctr) ^ (uint64_t)r);
+            const uint64_t hh = mix64(mix64(mix64(seed) ^ ctr) ^ (uint64_t)r);
             const float u = (float)(hh >> 40) * (1.0f / 16777216.0f);
             float c = 0.f;
             int last = 0;
@@ -657,38 +651,9 @@ __device__ __forceinline__ void cnn_loss_row(const float (&zr)[AM + 1], float v,
     }
     H = -H;
     if (la.normalize) adv = (adv - meanf) / (stdf + 1e-8f);
-    const float ratio = expf(lp - olp);
-    const float rc = fminf(fmaxf(ratio, la.clip_lo), la.clip_hi);
-    const float s1 = adv * ratio, s2 = adv * rc;
-    const float mn = fminf(s1, s2);
-    const float vdelta = v - ov;
-    const float du = v - ret;
-    const float vu = du * du;
-    const float vcl = ov + fminf(fmaxf(vdelta, -la.clip_vf), la.clip_vf);
-    const float dc = vcl - ret;
-    const float vc = dc * dc;
-    const float ldiff = fminf(fmaxf(lp - olp, -20.0f), 20.0f);
-    const float r2 = expf(ldiff);
-    const float rv = ret - v;
-    acc[0] += (double)mn;
-    acc[1] += (double)fmaxf(vu, vc);
-    acc[2] += (double)H;
-    acc[3] += (ratio < la.clip_lo || ratio > la.clip_hi) ? 1.0 : 0.0;
-    acc[4] += (vdelta < -la.clip_vf || vdelta > la.clip_vf) ? 1.0 : 0.0;
-    acc[5] += (double)(olp - lp);
-    acc[6] += (double)((r2 - 1.0f) - logf(r2));
-    acc[7] += (double)rv;
-    acc[8] += (double)rv * (double)rv;
-    acc[9] += (double)ret;
-    acc[10] += (double)ret * (double)ret;
-    acc[11] += (double)adv;
-    acc[12] += (double)adv * (double)adv;
-    const float ga = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float gb = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float inclip = (ratio >= la.clip_lo && ratio <= la.clip_hi) ? 1.0f : 0.0f;
-    const float g_mn = -invB;
-    const float dratio = adv * (g_mn * ga) + adv * (g_mn * gb) * inclip;
-    const float dlp = dratio * ratio;
+    const PpoRowTerms t = ppo_row_terms(lp, olp, v, ov, adv, ret, la);
+    ppo_row_sums(t, H, lp, olp, v, adv, ret, la, acc);
+    const float dlp = ppo_row_dlp(t, adv, la, invB);
     const float dH = -la.ent_coef * invB;
     float dzv[AM];
 #pragma unroll
@@ -702,11 +667,7 @@ __device__ __forceinline__ void cnn_loss_row(const float (&zr)[AM + 1], float v,
 #pragma unroll
     for (int a = 0; a < AM; ++a)
         if (a < A) dzr[a] = dzv[a];
-    const float hu = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float hc = vc > vu ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float invc = (vdelta >= -la.clip_vf && vdelta <= la.clip_vf) ? 1.0f : 0.0f;
-    const float gv = la.vf_coef * invB;
-    dzr[A] = (gv * hu) * (2.0f * du) + (gv * hc) * (2.0f * dc) * invc;
+    dzr[A] = ppo_row_dvalue(t, la, invB);
 }
 
 // batch advantage normalisation statistics (utils/torch.py:97-99): mean and unbiased std over the
@@ -781,8 +742,7 @@ __global__ __launch_bounds__(256) void k_cnn_loss(const float *__restrict__ z, c
         for (int q = 0; q < kSums; ++q) part[(int64_t)blockIdx.x * kSums + q] = acc[q];
 }
 
-// ---- loss metrics from the row-block partial sums (summed in block order) + KL early stop
-// the minibatch record from the loss row-block partial sums (summed in block order) + the KL
+// ---- the minibatch record from the loss row-block partial sums (summed in block order) + the KL
 // early stop (agents/base_agent.py:330-366); one thread
 __device__ void cnn_write_metrics(const double *__restrict__ part, int nb, int B, const LossArgs &la,
                                   float *__restrict__ metrics, int32_t *__restrict__ stop)
@@ -800,33 +760,8 @@ __device__ void cnn_write_metrics(const double *__restrict__ part, int nb, int B
         for (int b = 0; b < nb; ++b) v += part[(int64_t)b * kSums + q];
         t[q] = v;
     }
-    const double Bd = (double)B;
-    const float pl = (float)(-t[0] / Bd);
-    const float vl = (float)(t[1] / Bd);
-    const float ent = (float)(t[2] / Bd);
-    const float loss = pl + la.vf_coef * vl + la.ent_coef * (-ent);
-    const double var_rv = (t[8] - t[7] * t[7] / Bd) / (Bd - 1.0);
-    const double var_r = (t[10] - t[9] * t[9] / Bd) / (Bd - 1.0);
-    const double amean = t[11] / Bd;
-    const double astd = sqrt(fmax(0.0, (t[12] - t[11] * t[11] / Bd) / (Bd - 1.0)));
-    const float approx_kl = (float)(t[6] / Bd);
-    const bool kl_stop = la.target_kl > 0.0f && approx_kl > la.target_kl;
-    metrics[GS_M_LOSS] = loss;
-    metrics[GS_M_POLICY_LOSS] = pl;
-    metrics[GS_M_VALUE_LOSS] = vl;
-    metrics[GS_M_ENTROPY] = ent;
-    metrics[GS_M_CLIP_FRAC] = (float)(t[3] / Bd);
-    metrics[GS_M_CLIP_FRAC_VF] = (float)(t[4] / Bd);
-    metrics[GS_M_EXPLAINED_VAR] = (float)(1.0 - var_rv / var_r);
-    metrics[GS_M_KL] = (float)(t[5] / Bd);
-    metrics[GS_M_APPROX_KL] = approx_kl;
-    metrics[GS_M_ADV_NORM_MEAN] = la.normalize ? (float)amean : 0.0f;
-    metrics[GS_M_ADV_NORM_STD] = la.normalize ? (float)astd : 0.0f;
-    metrics[GS_M_KL_STOP] = kl_stop ? 1.0f : 0.0f;
+    const bool kl_stop = write_metrics(t, (double)B, la, metrics, true);
     metrics[GS_M_GRAD_NORM] = 0.0f;
-    metrics[GS_M_SKIPPED] = kl_stop ? 1.0f : 0.0f;
-    metrics[GS_M_UNEVALUATED] = 0.0f;
-    metrics[GS_M_RES1] = 0.0f;
     if (kl_stop && stop) *stop = 1;
 }
 
@@ -887,40 +822,9 @@ __device__ __forceinline__ void cnn_loss_lanes(float za, float v, int act, float
     const float pg = masked ? seg_sum(pgc) : 0.f;
     const float lp = __shfl(va ? ln : 0.f, min(max(act, 0), 31), 32) * (float)(act >= 0 && act < 32);
     if (la.normalize) adv = (adv - meanf) / (stdf + 1e-8f);
-    const float ratio = expf(lp - olp);
-    const float rc = fminf(fmaxf(ratio, la.clip_lo), la.clip_hi);
-    const float s1 = adv * ratio, s2 = adv * rc;
-    const float mn = fminf(s1, s2);
-    const float vdelta = v - ov;
-    const float du = v - ret;
-    const float vu = du * du;
-    const float vcl = ov + fminf(fmaxf(vdelta, -la.clip_vf), la.clip_vf);
-    const float dc = vcl - ret;
-    const float vc = dc * dc;
-    if (a == 0 && live) {
-        const float ldiff = fminf(fmaxf(lp - olp, -20.0f), 20.0f);
-        const float r2 = expf(ldiff);
-        const float rv = ret - v;
-        acc[0] += (double)mn;
-        acc[1] += (double)fmaxf(vu, vc);
-        acc[2] += (double)H;
-        acc[3] += (ratio < la.clip_lo || ratio > la.clip_hi) ? 1.0 : 0.0;
-        acc[4] += (vdelta < -la.clip_vf || vdelta > la.clip_vf) ? 1.0 : 0.0;
-        acc[5] += (double)(olp - lp);
-        acc[6] += (double)((r2 - 1.0f) - logf(r2));
-        acc[7] += (double)rv;
-        acc[8] += (double)rv * (double)rv;
-        acc[9] += (double)ret;
-        acc[10] += (double)ret * (double)ret;
-        acc[11] += (double)adv;
-        acc[12] += (double)adv * (double)adv;
-    }
-    const float ga = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float gb = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float inclip = (ratio >= la.clip_lo && ratio <= la.clip_hi) ? 1.0f : 0.0f;
-    const float g_mn = -invB;
-    const float dratio = adv * (g_mn * ga) + adv * (g_mn * gb) * inclip;
-    const float dlp = dratio * ratio;
+    const PpoRowTerms t = ppo_row_terms(lp, olp, v, ov, adv, ret, la);
+    if (a == 0 && live) ppo_row_sums(t, H, lp, olp, v, adv, ret, la, acc);
+    const float dlp = ppo_row_dlp(t, adv, la, invB);
     const float dH = -la.ent_coef * invB;
     const float pe = expf(ln);
     float gg = dlp * ((a == act ? 1.0f : 0.0f) - pe);
@@ -932,11 +836,7 @@ __device__ __forceinline__ void cnn_loss_lanes(float za, float v, int act, float
         if (dz_global) dz_global[a] = dza;
     }
     if (a == 0) {
-        const float hu = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-        const float hc = vc > vu ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-        const float invc = (vdelta >= -la.clip_vf && vdelta <= la.clip_vf) ? 1.0f : 0.0f;
-        const float gv = la.vf_coef * invB;
-        const float dzv = live ? (gv * hu) * (2.0f * du) + (gv * hc) * (2.0f * dc) * invc : 0.f;
+        const float dzv = live ? ppo_row_dvalue(t, la, invB) : 0.f;
         dzr[A] = dzv;
         if (dz_global) dz_global[A] = dzv;
     }
@@ -2065,35 +1965,6 @@ int backward_trunk(const float *P, const CnnLayout &L, const FrameSrc &fs, int64
     }
     if ((rc = colsum(w.da1, L.rows1(B), L.c1, w.parts, G + L.ob1, s))) return rc;
     return conv_wgrad_u8(s, bf, geom1(L, B), fs, w.da1, w.parts, kSplitW1, G + L.oW1);
-}
-
-AdamArgs adam_args(const gs_ppo_hparams &hp, int64_t t)
-{
-    AdamArgs a{};
-    const double b1 = hp.adam_beta1, b2 = hp.adam_beta2;
-    const double bc1 = 1.0 - pow(b1, (double)t), bc2 = 1.0 - pow(b2, (double)t);
-    a.max_norm = hp.max_grad_norm;
-    a.one_minus_b1 = (float)(1.0 - b1);
-    a.b2 = hp.adam_beta2;
-    a.one_minus_b2 = (float)(1.0 - b2);
-    a.neg_step_size = (float)(-(double)hp.lr / bc1);
-    a.bc2_sqrt = (float)sqrt(bc2);
-    a.eps = hp.adam_eps;
-    a.grad_scale = 1.0f;
-    return a;
-}
-
-LossArgs loss_args(const gs_ppo_hparams &hp)
-{
-    LossArgs la{};
-    la.clip_lo = (float)(1.0 - (double)hp.clip_range);
-    la.clip_hi = (float)(1.0 + (double)hp.clip_range);
-    la.clip_vf = hp.clip_range_vf;
-    la.vf_coef = hp.vf_coef;
-    la.ent_coef = hp.ent_coef;
-    la.target_kl = hp.target_kl;
-    la.normalize = hp.normalize_adv;
-    return la;
 }
 
 // row-parallel masked-categorical PPO loss (dlogits into dz) + one metrics/KL-stop block

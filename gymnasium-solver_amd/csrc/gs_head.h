@@ -1,8 +1,13 @@
-// gs_head.h — the per-row arithmetic the MLP kernels of gs_mlp.hip (two hidden layers) and
-// gs_mlp1.hip (one hidden layer) share, so both round identically: the categorical head
-// (log-softmax statistics, action select, log-prob), one row of the PPO loss with its analytic
-// gradients, the metric record, the fixed-order block sum, the clip coefficient and one
-// parameter's Adam step.  Both files compile with -ffp-contract=off.
+// gs_head.h — the per-row arithmetic every policy's kernels share: the categorical head
+// (log-softmax statistics, action select, log-prob), one row of the PPO loss in pieces (the
+// categorical row, the PPO terms, their metric sums and analytic gradients), the metric record,
+// the fixed-order block sum, the clip coefficient and one parameter's Adam step.
+// Included by gs_mlp.hip (two hidden layers), gs_mlp1.hip (one hidden layer), gs_mc.hip, gs_cnn.hip
+// (NatureCNN: the PPO terms, the record and mix64 under its own masked head) and, through
+// gs_pg_head.h, gs_pg.hip (REINFORCE: the categorical row and the Adam step).
+// "Round identically" holds between gs_mlp.hip and gs_mlp1.hip, which compile with
+// -ffp-contract=off; gs_cnn.hip and gs_pg.hip compile with the default contraction (FMA), so the
+// same source there may round a mul + add once where the MLP files round twice.
 #pragma once
 
 #include <float.h>
@@ -179,22 +184,23 @@ __device__ __forceinline__ void head_act_row(const float (&z)[AMAX + 1], int A, 
 }
 
 // ------------------------------------------------------------------------------------
-// One minibatch row of PPOAgent.losses_for_batch (agents/ppo/ppo_agent.py:21-152) with its
-// analytic gradients: z = raw logits | value, adv already batch-normalised.  Writes
-// dLoss/dlogits | dLoss/dvalue to dzr and adds the row's terms to the 14 metric sums.
+// The categorical row of a loss (Categorical: utils/distributions.py): from the raw logits z and
+// the taken action, ln = normalised logits, p = softmax(ln) (Categorical.probs), the entropy H and
+// the taken log-prob lp.  Shared by loss_row and pg_loss_row (gs_pg_head.h).
 // ------------------------------------------------------------------------------------
 template <int AMAX>
-__device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int act, float olp, float ov, float adv,
-                                         float ret, const LossArgs &la, float invB, float *__restrict__ dzr,
-                                         double (&acc)[kNumSums])
+struct CatRow {
+    float ln[AMAX], p[AMAX];   // normalised logits, softmax(ln) (Categorical.probs)
+    float H, lp;               // entropy, the taken action's log-prob
+};
+
+template <int AMAX>
+__device__ __forceinline__ CatRow<AMAX> cat_row(const float (&z)[AMAX + 1], int A, int act)
 {
-    float v = 0.0f;
-#pragma unroll
-    for (int a = 0; a < AMAX + 1; ++a)
-        if (a == A) v = z[a];
     const HeadRow h = head_stats<AMAX>(z, A);
     const float invS = 1.0f / h.S;
-    // ln = normalised logits, p = softmax(ln) (Categorical.probs), pe = exp(ln)
+    // local arrays, copied out below: filled through the result (or through reference parameters)
+    // the compiler no longer merges p's expf with head_stats' for every action (one more per row)
     float ln[AMAX], p[AMAX];
     float H = 0.0f, lp = 0.0f;
 #pragma unroll
@@ -206,27 +212,82 @@ __device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int 
             if (a == act) lp = ln[a];
         }
     }
-    H = -H;
-    const float ratio = expf(lp - olp);
-    const float rc = fminf(fmaxf(ratio, la.clip_lo), la.clip_hi);
-    const float s1 = adv * ratio, s2 = adv * rc;
-    const float mn = fminf(s1, s2);
-    const float vdelta = v - ov;
-    const float du = v - ret;
-    const float vu = du * du;
-    const float vcl = ov + fminf(fmaxf(vdelta, -la.clip_vf), la.clip_vf);
-    const float dc = vcl - ret;
-    const float vc = dc * dc;
-    const float vmax = fmaxf(vu, vc);
+    CatRow<AMAX> c;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) c.ln[a] = ln[a], c.p[a] = p[a];
+    c.H = -H;
+    c.lp = lp;
+    return c;
+}
+
+// one row of the approx_kl estimate (r - 1) - log r, the log-ratio clamped to +-20
+__device__ __forceinline__ float approx_kl_row(float lp, float olp)
+{
     const float ldiff = fminf(fmaxf(lp - olp, -20.0f), 20.0f);
     const float r2 = expf(ldiff);
-    const float akl = (r2 - 1.0f) - logf(r2);
+    return (r2 - 1.0f) - logf(r2);
+}
+
+// dLoss/dlogits of a row from dlp = dLoss/d(taken log-prob) and dH = dLoss/d(entropy)
+template <int AMAX>
+__device__ __forceinline__ void cat_row_grad(const CatRow<AMAX> &c, int A, int act, float dlp, float dH,
+                                             float *__restrict__ dzr)
+{
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a) {
+        if (a < A) {
+            const float pe = expf(c.ln[a]);   // softmax(z) as seen by logsumexp backward
+            float g = dlp * ((a == act ? 1.0f : 0.0f) - pe);
+            g += dH * (-c.p[a] * (c.ln[a] + c.H));
+            dzr[a] = g;
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// The PPO terms of one minibatch row (PPOAgent.losses_for_batch, agents/ppo/ppo_agent.py:21-152)
+// from its taken log-prob lp, value v and (normalised) advantage: the clipped surrogate, the
+// clipped value loss, the row's 13 metric sums and the gradients with respect to lp and v.  The
+// distribution (how lp and the entropy H come from the logits) is the caller's: loss_row below,
+// the (Masked)Categorical rows of gs_cnn.hip.
+// ------------------------------------------------------------------------------------
+struct PpoRowTerms {
+    float ratio, s1, s2, mn;   // exp(lp - olp), adv ratio, adv clamp(ratio), min(s1, s2)
+    float vdelta;              // v - ov
+    float du, vu, dc, vc;      // v - ret and its square; the same of the clipped value
+};
+
+__device__ __forceinline__ PpoRowTerms ppo_row_terms(float lp, float olp, float v, float ov, float adv, float ret,
+                                                     const LossArgs &la)
+{
+    PpoRowTerms t;
+    t.ratio = expf(lp - olp);
+    const float rc = fminf(fmaxf(t.ratio, la.clip_lo), la.clip_hi);
+    t.s1 = adv * t.ratio, t.s2 = adv * rc;
+    t.mn = fminf(t.s1, t.s2);
+    t.vdelta = v - ov;
+    t.du = v - ret;
+    t.vu = t.du * t.du;
+    const float vcl = ov + fminf(fmaxf(t.vdelta, -la.clip_vf), la.clip_vf);
+    t.dc = vcl - ret;
+    t.vc = t.dc * t.dc;
+    return t;
+}
+
+// adds the row's terms to the metric sums 0..12 (write_metrics reads them)
+template <int NS>
+__device__ __forceinline__ void ppo_row_sums(const PpoRowTerms &t, float H, float lp, float olp, float v, float adv,
+                                             float ret, const LossArgs &la, double (&acc)[NS])
+{
+    static_assert(NS >= 13, "the PPO row has 13 metric sums");
+    const float vmax = fmaxf(t.vu, t.vc);
+    const float akl = approx_kl_row(lp, olp);
     const float rv = ret - v;
-    acc[0] += (double)mn;
+    acc[0] += (double)t.mn;
     acc[1] += (double)vmax;
     acc[2] += (double)H;
-    acc[3] += (ratio < la.clip_lo || ratio > la.clip_hi) ? 1.0 : 0.0;
-    acc[4] += (vdelta < -la.clip_vf || vdelta > la.clip_vf) ? 1.0 : 0.0;
+    acc[3] += (t.ratio < la.clip_lo || t.ratio > la.clip_hi) ? 1.0 : 0.0;
+    acc[4] += (t.vdelta < -la.clip_vf || t.vdelta > la.clip_vf) ? 1.0 : 0.0;
     acc[5] += (double)(olp - lp);
     acc[6] += (double)akl;
     acc[7] += (double)rv;
@@ -235,33 +296,54 @@ __device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int 
     acc[10] += (double)ret * (double)ret;
     acc[11] += (double)adv;
     acc[12] += (double)adv * (double)adv;
-    // ---- analytic gradients (torch autograd tie rules: min/max ties split halves)
-    const float ga = s1 < s2 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float gb = s2 < s1 ? 1.0f : (s1 == s2 ? 0.5f : 0.0f);
-    const float inclip = (ratio >= la.clip_lo && ratio <= la.clip_hi) ? 1.0f : 0.0f;
-    const float g_mn = -invB;
-    const float dratio = adv * (g_mn * ga) + adv * (g_mn * gb) * inclip;
-    const float dlp = dratio * ratio;
-    const float dH = -la.ent_coef * invB;
-#pragma unroll
-    for (int a = 0; a < AMAX; ++a) {
-        if (a < A) {
-            const float pe = expf(ln[a]);   // softmax(z) as seen by logsumexp backward
-            float g = dlp * ((a == act ? 1.0f : 0.0f) - pe);
-            g += dH * (-p[a] * (ln[a] + H));
-            dzr[a] = g;
-        }
-    }
-    const float hu = vu > vc ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float hc = vc > vu ? 1.0f : (vu == vc ? 0.5f : 0.0f);
-    const float invc = (vdelta >= -la.clip_vf && vdelta <= la.clip_vf) ? 1.0f : 0.0f;
-    const float gv = la.vf_coef * invB;
-    dzr[A] = (gv * hu) * (2.0f * du) + (gv * hc) * (2.0f * dc) * invc;
 }
 
-// metrics record from the 14 sums (shared by k_loss, the fused path's k_metrics_all and the
-// one-hidden-layer update)
-__device__ __forceinline__ void write_metrics(const double *t, double Bd, const LossArgs &la, float *metrics,
+// dLoss/dlp of the clipped surrogate (torch autograd tie rules: min/max ties split halves)
+__device__ __forceinline__ float ppo_row_dlp(const PpoRowTerms &t, float adv, const LossArgs &la, float invB)
+{
+    const float ga = t.s1 < t.s2 ? 1.0f : (t.s1 == t.s2 ? 0.5f : 0.0f);
+    const float gb = t.s2 < t.s1 ? 1.0f : (t.s1 == t.s2 ? 0.5f : 0.0f);
+    const float inclip = (t.ratio >= la.clip_lo && t.ratio <= la.clip_hi) ? 1.0f : 0.0f;
+    const float g_mn = -invB;
+    const float dratio = adv * (g_mn * ga) + adv * (g_mn * gb) * inclip;
+    return dratio * t.ratio;
+}
+
+// dLoss/dvalue of the clipped value loss (the same tie rule)
+__device__ __forceinline__ float ppo_row_dvalue(const PpoRowTerms &t, const LossArgs &la, float invB)
+{
+    const float hu = t.vu > t.vc ? 1.0f : (t.vu == t.vc ? 0.5f : 0.0f);
+    const float hc = t.vc > t.vu ? 1.0f : (t.vu == t.vc ? 0.5f : 0.0f);
+    const float invc = (t.vdelta >= -la.clip_vf && t.vdelta <= la.clip_vf) ? 1.0f : 0.0f;
+    const float gv = la.vf_coef * invB;
+    return (gv * hu) * (2.0f * t.du) + (gv * hc) * (2.0f * t.dc) * invc;
+}
+
+// ------------------------------------------------------------------------------------
+// One minibatch row of the MLP policies' PPO loss with its analytic gradients: z = raw logits |
+// value, adv already batch-normalised.  Writes dLoss/dlogits | dLoss/dvalue to dzr and adds the
+// row's terms to the 14 metric sums.
+// ------------------------------------------------------------------------------------
+template <int AMAX>
+__device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int act, float olp, float ov, float adv,
+                                         float ret, const LossArgs &la, float invB, float *__restrict__ dzr,
+                                         double (&acc)[kNumSums])
+{
+    float v = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AMAX + 1; ++a)
+        if (a == A) v = z[a];
+    const CatRow<AMAX> c = cat_row<AMAX>(z, A, act);
+    const PpoRowTerms t = ppo_row_terms(c.lp, olp, v, ov, adv, ret, la);
+    ppo_row_sums(t, c.H, c.lp, olp, v, adv, ret, la, acc);
+    cat_row_grad<AMAX>(c, A, act, ppo_row_dlp(t, adv, la, invB), -la.ent_coef * invB, dzr);
+    dzr[A] = ppo_row_dvalue(t, la, invB);
+}
+
+// metrics record from the sums 0..12 (shared by k_loss, the fused path's k_metrics_all, the
+// one-hidden-layer update and the NatureCNN's cnn_write_metrics); GS_M_GRAD_NORM is the caller's.
+// Returns whether approx_kl passed target_kl (the KL early stop)
+__device__ __forceinline__ bool write_metrics(const double *t, double Bd, const LossArgs &la, float *metrics,
                                               bool adv_stats)
 {
     const float pl = (float)(-t[0] / Bd);
@@ -291,6 +373,7 @@ __device__ __forceinline__ void write_metrics(const double *t, double Bd, const 
     metrics[GS_M_SKIPPED] = kl_stop ? 1.0f : 0.0f;
     metrics[GS_M_UNEVALUATED] = 0.0f;
     metrics[GS_M_RES1] = 0.0f;
+    return kl_stop;
 }
 
 }  // namespace gs

@@ -111,6 +111,11 @@ __host__ __device__ constexpr int round4(int n) { return (n + 3) & ~3; }
 // kNumSums (the metric sums of one minibatch) and block_reduce (the fixed-order 256-thread sum):
 // gs_head.h
 
+// Per-component pre-clip gradient norms of one step (utils/models.py:196-230 compute_grad_norms,
+// recorded at agents/base_agent.py:607-608): policy_head and value_head from their gradients in G,
+// backbone as the rest of the step's squared total (every component of the MLP policy is one of
+// the three).  hq: this thread's {policy, value} sums of squares; every thread of the block calls
+// it (threads 0..255 contribute); scratch: 2 x (256 + 16) doubles; thread 0 writes the record.
 __device__ __forceinline__ void store_component_norms(double (&hq)[2], double total_sq, float gscale, float *rec,
                                                       double *scratch)
 {
@@ -169,13 +174,6 @@ __device__ __forceinline__ void copy_to_lds(float *dst, const float *src, int n)
     }
 }
 
-// Per-component pre-clip gradient norms of one step (utils/models.py:196-230 compute_grad_norms,
-// recorded at agents/base_agent.py:607-608): policy_head and value_head from their gradients in G,
-// backbone as the rest of the step's squared total (every component of the MLP policy is one of
-// the three).  hq: this thread's {policy, value} sums of squares; every thread of the block calls
-// it (threads 0..255 contribute); scratch: 2 x (256 + 16) doubles; thread 0 writes the record.
-__device__ __forceinline__ void store_component_norms(double (&hq)[2], double total_sq, float gscale, float *rec,
-                                                      double *scratch);
 // head gradient u of the flat head index space: u < A1*H2 the weight rows (policy rows 0..A-1, then
 // the value row), past it the A1 biases; *value = whether it belongs to the value head
 __host__ __device__ inline int64_t head_grad_offset(const Layout &L, int u, bool *value)
@@ -204,14 +202,6 @@ size_t fwd_lds_bytes(const Layout &L)
                round4(kTile * L.D) + kTile * (L.H1 + 4) + 1024 + kTile * 17;
     return n * sizeof(float);
 }
-
-template <int AMAX, int AEX>
-__device__ __forceinline__ void gather_head_row(const float *__restrict__ zpart, const float *__restrict__ P,
-                                                const Layout &L, int64_t r, float (&z)[AMAX + 1]);
-template <int AMAX>
-__device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int act, float olp, float ov, float adv,
-                                         float ret, const LossArgs &la, float invB, float *__restrict__ dzr,
-                                         double (&acc)[14]);
 
 // FUSED (gs_ppo_update path): x comes pre-gathered (FusedFwd::xg, one load instead of the
 // index -> row -> obs chain).  The head combine stays in the next launch (k_loss_rows): an

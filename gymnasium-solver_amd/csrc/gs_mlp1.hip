@@ -16,6 +16,7 @@
 // The per-row head / loss / Adam arithmetic is gs_head.h's, shared with gs_mlp.hip.
 #include "gs_common.h"
 #include "gs_head.h"
+#include "gs_hparams.h"
 #include "gs_rollout1.h"
 #include "gs_tabular_env.h"
 #include "gs_cartpole_env.h"
@@ -672,24 +673,12 @@ int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const
     a.idx = idx, a.B = (int)batch, a.n = (int)n, a.step0 = adam_step0;
     a.metrics = metrics;
     a.stop = hp.target_kl > 0.0f && !loss_only ? stop_flag : nullptr;   // target_kl unset: neither read nor written
-    // the loss and optimizer constants exactly as the two-hidden-layer path forms them (gs_ppo.hip make_step_args)
+    a.la = loss_args(hp);
     a.la.batch_rows = (int)batch;
     a.la.inv_batch = 1.0f / (float)batch;
-    a.la.clip_lo = (float)(1.0 - (double)hp.clip_range);
-    a.la.clip_hi = (float)(1.0 + (double)hp.clip_range);
-    a.la.clip_vf = hp.clip_range_vf;
-    a.la.vf_coef = hp.vf_coef;
-    a.la.ent_coef = hp.ent_coef;
-    a.la.target_kl = hp.target_kl;
-    a.la.normalize = hp.normalize_adv;
     const double b1 = hp.adam_beta1, b2 = hp.adam_beta2;
     GS_REQUIRE(loss_only || (b1 > 0.0 && b1 < 1.0 && b2 > 0.0 && b2 < 1.0), "Adam betas must lie in (0, 1)");
-    a.aa.max_norm = hp.max_grad_norm;
-    a.aa.one_minus_b1 = (float)(1.0 - b1);
-    a.aa.b2 = (float)b2;
-    a.aa.one_minus_b2 = (float)(1.0 - b2);
-    a.aa.eps = hp.adam_eps;
-    a.aa.grad_scale = 1.0f;
+    a.aa = adam_args(hp, adam_step0 + 1);   // the kernel forms each step's schedule itself, from lr and the logs below
     a.lr = (double)hp.lr;
     a.ln_b1 = loss_only ? 0.0 : log(b1);
     a.ln_b2 = loss_only ? 0.0 : log(b2);

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "gs_hparams.h"
 #include "gs_pg_head.h"
 
 namespace gs {
@@ -434,19 +435,8 @@ int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_m
         sa.groups = ws.groups, sa.stride = ws.stride, sa.B = (int)batch, sa.normalize = ra.normalize;
         sa.do_step = do_step ? 1 : 0;
         sa.ent_coef = hp.ent_coef;
-        if (do_step) {      // the optimizer constants as the PPO path forms them (gs_ppo.hip make_step_args)
-            const double t = (double)(adam_step0 + k + 1);
-            sa.aa.max_norm = hp.max_grad_norm;
-            sa.aa.one_minus_b1 = (float)(1.0 - b1);
-            sa.aa.b2 = (float)b2;
-            sa.aa.one_minus_b2 = (float)(1.0 - b2);
-            const double bc1 = 1.0 - pow(b1, t), bc2 = 1.0 - pow(b2, t);
-            sa.aa.neg_step_size = (float)(-(double)hp.lr / bc1);
-            sa.aa.bc2_sqrt = (float)sqrt(bc2);
-            sa.aa.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-            sa.aa.eps = hp.adam_eps;
-            sa.aa.grad_scale = 1.0f;
-        }
+        if (do_step)
+            sa.aa = adam_args(hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps, hp.max_grad_norm, adam_step0 + k + 1);
         hipLaunchKernelGGL(k_pg_step, dim3(step_groups), dim3(256), 0, s, L, sa);
         GS_LAUNCH_CHECK("k_pg_step");
     }

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "gs_comm_internal.h"
+#include "gs_hparams.h"
 #include "gs_cartpole_env.h"
 #include "gs_acrobot_env.h"
 #include "gs_mountaincar_env.h"
@@ -397,6 +398,7 @@ StepArgs make_step_args(const gs_ppo_hparams &hp, const Layout &L, int64_t B, in
                         const gs_ppo_global *glob = nullptr)
 {
     StepArgs a{};
+    a.la = loss_args(hp);
     a.la.batch_rows = (int)(glob ? glob->batch_global : B);
     a.la.inv_batch = 1.0f / (float)a.la.batch_rows;
     if (glob) {
@@ -404,27 +406,9 @@ StepArgs make_step_args(const gs_ppo_hparams &hp, const Layout &L, int64_t B, in
         a.la.sums_out = glob->metric_sums;
         a.sum_exchange = true;
     }
-    a.la.clip_lo = (float)(1.0 - (double)hp.clip_range);
-    a.la.clip_hi = (float)(1.0 + (double)hp.clip_range);
-    a.la.clip_vf = hp.clip_range_vf;
-    a.la.vf_coef = hp.vf_coef;
-    a.la.ent_coef = hp.ent_coef;
-    a.la.target_kl = hp.target_kl;
-    a.la.normalize = hp.normalize_adv;
     a.la.bf16 = (hp.flags & GS_HP_BF16) ? 1 : 0;
     a.act_stats = (hp.flags & GS_HP_ACT_STATS) && !glob;
-    const double b1 = hp.adam_beta1, b2 = hp.adam_beta2;
-    a.aa.max_norm = hp.max_grad_norm;
-    a.aa.one_minus_b1 = (float)(1.0 - b1);
-    a.aa.b2 = (float)b2;
-    a.aa.one_minus_b2 = (float)(1.0 - b2);
-    const double bc1 = 1.0 - pow(b1, (double)t);
-    const double bc2 = 1.0 - pow(b2, (double)t);
-    a.aa.neg_step_size = (float)(-(double)hp.lr / bc1);
-    a.aa.bc2_sqrt = (float)sqrt(bc2);
-    a.aa.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
-    a.aa.eps = hp.adam_eps;
-    a.aa.grad_scale = 1.0f;
+    a.aa = adam_args(hp, t);
     a.aa.n_slots = n_sumsq_slots(L);
     a.aa.nrb = (int)((B + rows_b(L, B) - 1) / rows_b(L, B));
     return a;

@@ -14,9 +14,11 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 # the sources each measured path is compiled from: the MLP minibatch chain + GAE (C2/C3 PMC
 # passes, tools/pmc_run.py) and the NatureCNN update (C4 per-kernel passes, tools/cnn_kernel_run.py)
 PATH_SOURCES = {
-    "mlp": ("gs_mlp.hip", "gs_ppo.hip", "gs_gae.hip", "gs_common.h", "gs_head.h", "gs_xgmi_dev.h", "gs_synth_env.h",
-            "gs_env_episode.h", "gs_cartpole_env.h", "gs_acrobot_env.h", "gs_mountaincar_env.h", "gs_bandit_env.h"),
-    "cnn": ("gs_cnn.hip", "gs_conv.hip", "gs_gemm.hip", "gs_fc.hip", "gs_common.h", "gs_conv.h", "gs_gemm.h"),
+    "mlp": ("gs_mlp.hip", "gs_ppo.hip", "gs_gae.hip", "gs_common.h", "gs_head.h", "gs_hparams.h", "gs_xgmi_dev.h",
+            "gs_synth_env.h", "gs_env_episode.h", "gs_cartpole_env.h", "gs_acrobot_env.h", "gs_mountaincar_env.h",
+            "gs_bandit_env.h"),
+    "cnn": ("gs_cnn.hip", "gs_conv.hip", "gs_gemm.hip", "gs_fc.hip", "gs_common.h", "gs_conv.h", "gs_gemm.h",
+            "gs_head.h", "gs_hparams.h"),
 }
 
 

@@ -171,6 +171,17 @@ def test_cnn_update_gathered_rows_and_generic_shapes(cuda, in_shape, T):
     ws = torch.empty(int(lib.gs_cnn_workspace_bytes(pm.dims, B)), dtype=torch.uint8, device=cuda)
     met_d = torch.zeros(GS_NUM_METRICS, device=cuda)
     stop = torch.zeros(1, dtype=torch.int32, device=cuda)
+    # the loss-only entry (row-parallel loss kernel + its record) on the same minibatch, before the
+    # update moves the parameters: the oracle's loss, and the same record from a second call
+    loss_recs = []
+    for _ in range(2):
+        met_l = torch.zeros(GS_NUM_METRICS, device=cuda)
+        check(lib.gs_cnn_ppo_loss(pm.params.data_ptr(), pm.dims, hp, view, idx_d.data_ptr(), B, met_l.data_ptr(), None,
+                                  ws.data_ptr(), torch.cuda.current_stream().cuda_stream), "gs_cnn_ppo_loss")
+        torch.cuda.synchronize()
+        loss_recs.append(met_l.cpu().numpy())
+    assert abs(loss_recs[0][0] - loss) < 1e-5 * max(1.0, abs(loss))
+    assert loss_recs[0].tobytes() == loss_recs[1].tobytes()
     check(lib.gs_cnn_ppo_update(pm.params.data_ptr(), grads.data_ptr(), m.data_ptr(), v.data_ptr(), pm.dims, hp, view,
                                 idx_d.data_ptr(), B, 1, 0, met_d.data_ptr(), stop.data_ptr(), ws.data_ptr(), None,
                                 torch.cuda.current_stream().cuda_stream), "gs_cnn_ppo_update")
