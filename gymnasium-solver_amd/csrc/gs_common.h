@@ -411,6 +411,14 @@ int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const
 int mlp1_activation_stats(const float *params, const gs_mlp_dims &d, const gs_rollout_view &ro, const int32_t *idx,
                           int64_t rows, double *part, hipStream_t s);
 
+// ---- exact-f32 MFMA (v_mfma_f32_16x16x4_f32): lane l holds A[l & 15][l >> 4] and B[l >> 4][l & 15];
+// C/D col = l & 15, row = 4 (l >> 4) + reg.  Bit-equal to a k-ordered fmaf chain.  Used by the update
+// chain (gs_mlp.hip) and the row-parallel update (gs_ppo_rows.hip).
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c)
+{
+    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
 // ---- bf16 MFMA operands of the NatureCNN path (GS_HP_BF16 performance mode) ----------------
 // 8 fp32 values -> one bf16 fragment of v_mfma_f32_16x16x32_bf16 / 32x32x16_bf16 (round to
 // nearest even: v_cvt_pk_bf16_f32); accumulation stays fp32

@@ -3,11 +3,12 @@
 // categorical row, the PPO terms, their metric sums and analytic gradients), the metric record,
 // the fixed-order block sum, the clip coefficient and one parameter's Adam step.
 // Included by gs_mlp.hip (two hidden layers), gs_mlp1.hip (one hidden layer), gs_mc.hip, gs_cnn.hip
-// (NatureCNN: the PPO terms, the record and mix64 under its own masked head) and, through
+// (NatureCNN: the PPO terms, the record and mix64 under its own masked head), gs_ppo_rows.hip (the
+// row-parallel PPO update: loss_row, write_metrics, block_reduce, clip_coef, adam_param) and, through
 // gs_pg_head.h, gs_pg.hip (REINFORCE: the categorical row and the Adam step).
 // "Round identically" holds between gs_mlp.hip and gs_mlp1.hip, which compile with
-// -ffp-contract=off; gs_cnn.hip and gs_pg.hip compile with the default contraction (FMA), so the
-// same source there may round a mul + add once where the MLP files round twice.
+// -ffp-contract=off; gs_cnn.hip, gs_pg.hip and gs_ppo_rows.hip compile with the default contraction
+// (FMA), so the same source there may round a mul + add once where the MLP files round twice.
 #pragma once
 
 #include <float.h>

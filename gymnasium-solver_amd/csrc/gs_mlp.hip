@@ -84,11 +84,6 @@ __device__ __forceinline__ void span_end(int kern, int64_t k)
 #define GS_SPAN_END(slot, k) ;
 #endif
 
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c)
-{
-    return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
 // bf16 mode: two K-chunks of 16 (lane quarter q's k = 4q..4q+3 of each chunk, the fp32 chain's
 // operand layout) as one v_mfma_f32_16x16x32_bf16 — elements 0..3 from chunk c, 4..7 from chunk
 // c + 1, the same order in both operands, so the product sums all 32 k; fp32 accumulation

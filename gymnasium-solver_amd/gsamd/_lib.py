@@ -141,6 +141,10 @@ def _load():
         "gs_pg_update": (ctypes.c_int, [vp, vp, vp, vp, MlpDims, PGHparams, RolloutView, vp, i64, i64, i64, vp, vp, sz,
                                         vp, vp]),
         "gs_pg_loss": (ctypes.c_int, [vp, vp, MlpDims, PGHparams, RolloutView, vp, i64, vp, vp, sz, vp]),
+        "gs_ppo_rows_workspace_bytes": (sz, [MlpDims, i64]),
+        "gs_ppo_rows_update": (ctypes.c_int, [vp, vp, vp, vp, MlpDims, PPOHparams, RolloutView, vp, i64, i64, i64, vp,
+                                              vp, vp, sz, vp, vp]),
+        "gs_ppo_rows_loss": (ctypes.c_int, [vp, vp, MlpDims, PPOHparams, RolloutView, vp, i64, vp, vp, sz, vp]),
         "gs_mlp_param_count": (i64, [MlpDims]),
         "gs_policy_scratch_bytes": (sz, [MlpDims, i64]),
         "gs_policy_act": (ctypes.c_int, [vp, MlpDims, vp, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
@@ -263,6 +267,7 @@ EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_norma
             "gs_ppo_workspace_bytes", "gs_ppo_minibatch_step", "gs_ppo_loss", "gs_mlp_activation_stats", "gs_ppo_stage", "gs_ppo_update",
             "gs_ppo_update_global", "gs_ppo_update_workspace_bytes",
             "gs_ppo_graph_cache_info", "gs_ppo_exchange_inside_bwd",
+            "gs_ppo_rows_workspace_bytes", "gs_ppo_rows_update", "gs_ppo_rows_loss",
             "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
             "gs_cnn_ppo_update_global",
             "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",

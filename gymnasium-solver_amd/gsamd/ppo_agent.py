@@ -39,6 +39,7 @@ from .metrics import NUM_SUMS, MetricsRecorder, ppo_keys, ppo_records
 from .schedules import SCHEDULABLE, build_schedulers
 
 STAGES = ("train",)
+ROWS_UPDATE_ABOVE = 1024            # the chain entries' largest minibatch; beyond it the row-parallel update
 BANDIT_MAX_TRAINABLE_ARMS = 15      # see _device_env: what the MLP update's forward staging covers
 
 
@@ -86,6 +87,7 @@ class DevicePPOAgent:
         # optional per-epoch (start, update-start, end) events on the launch stream (bench.py)
         self.phase_events = None
         self._check_one_layer_policy()
+        self._check_rows_update()
         self.build_env("train", env)
         self.build_models()
         self.build_rollout_collector("train")
@@ -104,6 +106,27 @@ class DevicePPOAgent:
         if str(getattr(c, "precision", "fp32")) == "bf16":
             raise ValueError(f"model_id {c.model_id!r} has one hidden layer: its update is fp32 only, "
                              "precision 'bf16' is a mode of the two-hidden-layer chain")
+
+    def _use_rows(self, B: int) -> bool:
+        """Minibatches beyond the chain's 1024 rows take the row-parallel update
+        (csrc/gs_ppo_rows.hip: gs_ppo_rows_update / gs_ppo_rows_loss); at 1024 rows and below
+        nothing changes."""
+        return not self.is_pixel and int(B) > ROWS_UPDATE_ABOVE
+
+    def _check_rows_update(self) -> None:
+        """batch_size > 1024 on an MLP policy runs the row-parallel update: fp32, one GPU, local
+        minibatches.  What it does not serve is refused here, before any device work."""
+        c = self.config
+        if not self._use_rows(c.batch_size):
+            return
+        what = f"batch_size {int(c.batch_size)} > {ROWS_UPDATE_ABOVE} runs the row-parallel PPO update"
+        if self.world_size > 1:
+            raise ValueError(f"{what}: it has no gradient exchange, world_size={self.world_size} is not supported "
+                             "(use one GPU)")
+        if str(getattr(c, "dp_mode", "local")) == "global":
+            raise ValueError(f"{what}: dp_mode 'global' is not supported (use dp_mode 'local')")
+        if str(getattr(c, "precision", "fp32")) == "bf16":
+            raise ValueError(f"{what}: it is fp32 only, precision 'bf16' is a mode of the two-hidden-layer chain")
 
     def build_env(self, stage: str, env=None):
         """BaseAgent.build_env (base_agent.py:129-192): the env the config names.  A passed env
@@ -399,6 +422,13 @@ class DevicePPOAgent:
             self._base_seed = seed0
         if self.is_pixel:
             ws = int(lib.gs_cnn_workspace_bytes(self.policy_model.dims, self.batch_size))
+        elif self._use_rows(self.batch_size):   # one partial slot per row workgroup
+            ws = int(lib.gs_ppo_rows_workspace_bytes(self.policy_model.dims, self.batch_size))
+            if ws == 0:
+                d = self.policy_model.dims
+                raise ValueError(f"batch_size {self.batch_size} with the policy {d.obs_dim}-{d.hidden1}-{d.hidden2}-"
+                                 f"{d.n_actions} is outside the row-parallel PPO update's envelope (include/gsamd.h, "
+                                 "gs_ppo_rows_update)")
         else:   # the whole update's workspace (fused chain: per-update gathered minibatch fields)
             ws = int(lib.gs_ppo_update_workspace_bytes(self.policy_model.dims, self.batch_size, self.n_minibatches))
         self.workspace = torch.zeros(ws, dtype=torch.uint8, device=self.device)
@@ -462,6 +492,7 @@ class DevicePPOAgent:
                   "act": torch.empty(1, B, dtype=torch.int64, device=dev),
                   **{k: torch.empty(1, B, dtype=torch.float32, device=dev) for k in ("lp", "v", "adv", "ret")}}
             ws_need = int(lib.gs_cnn_workspace_bytes(self.policy_model.dims, B) if pix else
+                          lib.gs_ppo_rows_workspace_bytes(self.policy_model.dims, B) if self._use_rows(B) else
                           lib.gs_ppo_workspace_bytes(self.policy_model.dims, B))
             st["ws"] = self.workspace if ws_need <= self.workspace.numel() else \
                 torch.zeros(ws_need, dtype=torch.uint8, device=dev)
@@ -497,6 +528,12 @@ class DevicePPOAgent:
             check(lib.gs_cnn_ppo_loss(ptr(self.policy_model.params), self.policy_model.dims, self.hparams(), view,
                                       ptr(idx), B, ptr(self._step_metrics), None, ptr(ws), stream_handle()),
                   "gs_cnn_ppo_loss")
+        elif self._use_rows(B):
+            if getattr(self, "_loss_grads", None) is None:      # the entry also leaves the unclipped gradient
+                self._loss_grads = torch.empty_like(self.grads)
+            check(lib.gs_ppo_rows_loss(ptr(self.policy_model.params), ptr(self._loss_grads), self.policy_model.dims,
+                                       self.hparams(), view, ptr(idx), B, ptr(self._step_metrics), ptr(ws), ws.numel(),
+                                       stream_handle()), "gs_ppo_rows_loss")
         else:
             check(lib.gs_ppo_loss(ptr(self.policy_model.params), self.policy_model.dims, self.hparams(), view,
                                   ptr(idx), B, ptr(self._step_metrics), ptr(ws), stream_handle()), "gs_ppo_loss")
@@ -530,6 +567,11 @@ class DevicePPOAgent:
                                         ptr(idx), B, 1, self.adam_step - 1, ptr(rec),
                                         ptr(self.stop_flag), ptr(ws), self.comm, stream_handle()),
                   "gs_cnn_ppo_update")
+        elif self._use_rows(B):
+            check(lib.gs_ppo_rows_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
+                                         ptr(self.adam_v), self.policy_model.dims, self.hparams(), view, ptr(idx), B, 1,
+                                         self.adam_step - 1, ptr(rec), ptr(self.stop_flag), ptr(ws), ws.numel(),
+                                         self.comm, stream_handle()), "gs_ppo_rows_update")
         else:
             check(lib.gs_ppo_minibatch_step(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
                                             ptr(self.adam_v), self.policy_model.dims, self.hparams(), view,
@@ -602,6 +644,12 @@ class DevicePPOAgent:
                                         self.batch_size, self.n_minibatches, self.adam_step, ptr(self.metrics_buf),
                                         ptr(self.stop_flag), ptr(self.workspace), self.comm, stream_handle()),
                   "gs_cnn_ppo_update")
+        elif self._use_rows(self.batch_size):
+            check(lib.gs_ppo_rows_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
+                                         ptr(self.adam_v), self.policy_model.dims, self.hparams(), buf.view(), ptr(idx),
+                                         self.batch_size, self.n_minibatches, self.adam_step, ptr(self.metrics_buf),
+                                         ptr(self.stop_flag), ptr(self.workspace), self.workspace.numel(), self.comm,
+                                         stream_handle()), "gs_ppo_rows_update")
         else:
             check(lib.gs_ppo_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
                                     ptr(self.adam_v), self.policy_model.dims, self.hparams(), buf.view(), ptr(idx),

@@ -467,6 +467,53 @@ int gs_pg_loss(const float *params_dev, float *grads_dev, gs_mlp_dims dims, gs_p
                const int32_t *idx_dev, int64_t batch, float *metrics_dev, void *workspace_dev, size_t workspace_bytes,
                void *stream);
 
+/* ---------------------------------------------------------------- PPO update, row-parallel (minibatches beyond 1024 rows)
+ * gs_ppo_update's semantics (PPOAgent.losses_for_batch + BaseAgent._backpropagate_and_step over
+ * n_minibatches * batch env-major indices, the same GS_NUM_METRICS record per minibatch, the same Adam
+ * state) for the one- and two-hidden-layer actor-critics on minibatches of up to 2^20 rows, where
+ * gs_ppo_update / gs_ppo_minibatch_step / gs_ppo_loss stop at 1024 (whole-minibatch tiles in LDS).  All
+ * parameters train: the value head is inside the loss.  Per optimizer step: the advantage sums (with
+ * normalize_adv), one row-parallel launch (workgroups own 16-row tiles and loop over them: forward, loss
+ * row, backward, their gradient share into their own partial slot; the H1 x H2 products of a two-layer
+ * net on v_mfma_f32_16x16x4_f32, exact f32), the slots summed in workgroup order, and the norms, clip,
+ * Adam and the record.  Every reduction has a fixed order (no float atomics): two runs give the same
+ * bytes, and one call of n minibatches equals n calls of one.
+ *   gs_ppo_rows_update: grads_dev is left holding the last applied step's clipped gradient.
+ *   gs_ppo_rows_loss:   forward, loss, record and the unclipped gradient (into grads_dev) of one
+ *                       minibatch; no optimizer step, no stop flag.
+ * Record: write_metrics' slots as gs_ppo_update, GS_M_GRAD_NORM and GS_M_GN_BACKBONE / _POLICY_HEAD /
+ * _VALUE_HEAD (pre-clip; 0 in the record of the minibatch that trips the KL stop, whose gradient is
+ * never summed), GS_M_GN_MLP 0.  hp.normalize_adv: (adv - mean) / (std_unbiased + 1e-8) over the
+ * minibatch's rows, the statistics in double in a fixed order.  hp.target_kl > 0: the sticky early stop
+ * described beside GS_NUM_METRICS; parameters, moments and gradient are then byte-identical to a run
+ * of that many steps fewer without a target; with the target unset stop_flag_dev is neither read nor
+ * written (and may be NULL).  GS_HP_ACT_STATS: GS_M_ACT + 4 l + {0..3} for l = 0 (backbone.0) and, with
+ * two hidden layers, l = 1 (backbone.2), over the minibatch's rows only (a ragged tile's padding rows
+ * count for nothing).
+ * Envelope: obs_dim in [1, 64]; hidden1 a multiple of 16 in [16, 512]; hidden2 0 (one hidden layer) or
+ * a multiple of 16 in [16, 512]; n_actions in [1, 32]; batch in [2, 2^20] (1024 and below included);
+ * T * N < 2^31.  Indices outside the rollout and actions outside [0, n_actions) are clamped.
+ * GS_E_INVALID before any launch, the reason in gs_last_error, for: a shape or batch outside the
+ * envelope, a non-NULL communicator, GS_HP_BF16, a workspace smaller than
+ * gs_ppo_rows_workspace_bytes(dims, batch) or not 16-byte aligned, parameters not 16-byte aligned, a
+ * NULL buffer, target_kl without a stop flag, and a row kernel whose static + dynamic LDS would pass
+ * 160 KB (none inside the envelope today: the widest net, 64-512-512-32, takes 155 392 bytes, all dynamic).
+ * Workspace (gs_ppo_rows_workspace_bytes; 0 = shape or batch not served), 256-byte aligned pieces:
+ * 64 x 2 doubles of advantage parts, 256 x 3 doubles of norm parts, then per row workgroup 14 doubles
+ * of metric sums, 4 doubles of activation sums, hidden1 + hidden2 u32 dead counts and one
+ * parameter-sized gradient slot (round4(P) floats).  Row workgroups = min(ceil(batch / 16), 256), so it
+ * grows with the batch up to 4096 rows and not beyond (4-256-256-2: 70 MB; 12-128-128-18: 21 MB;
+ * 64-512-512-32, the widest: 321 MB). */
+size_t gs_ppo_rows_workspace_bytes(gs_mlp_dims dims, int64_t batch);
+int gs_ppo_rows_update(float *params_dev, float *grads_dev, float *adam_m_dev, float *adam_v_dev,
+                       gs_mlp_dims dims, gs_ppo_hparams hp, gs_rollout_view rollout, const int32_t *idx_dev,
+                       int64_t batch, int64_t n_minibatches, int64_t adam_step0, float *metrics_dev,
+                       int32_t *stop_flag_dev, void *workspace_dev, size_t workspace_bytes,
+                       struct gs_comm *comm, void *stream);
+int gs_ppo_rows_loss(const float *params_dev, float *grads_dev, gs_mlp_dims dims, gs_ppo_hparams hp,
+                     gs_rollout_view rollout, const int32_t *idx_dev, int64_t batch, float *metrics_dev,
+                     void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* ---------------------------------------------------------------- NatureCNN actor-critic (C4/C5)
  * Replaces CNNActorCritic (utils/models.py:347-455; conv 8x8s4 -> 4x4s2 -> 3x3s1 with 32/64/64
  * channels, ReLU, Linear F->hidden ReLU, policy/value heads), action masking
