@@ -748,10 +748,7 @@ __device__ void cnn_write_metrics(const double *__restrict__ part, int nb, int B
                                   float *__restrict__ metrics, int32_t *__restrict__ stop)
 {
     if (stop && *stop) {
-        for (int k = 0; k < GS_NUM_METRICS; ++k) metrics[k] = 0.0f;
-        metrics[GS_M_SKIPPED] = 1.0f;
-        metrics[GS_M_KL_STOP] = 1.0f;
-        metrics[GS_M_UNEVALUATED] = 1.0f;
+        for (int k = 0; k < GS_NUM_METRICS; ++k) metrics[k] = unevaluated_slot(k);
         return;
     }
     double t[kSums];
@@ -2067,7 +2064,7 @@ __global__ __launch_bounds__(256) void k_act_stats_cols(float *__restrict__ x, i
             for (int u = 0; u < 4; ++u) {
                 v2[0] += (double)v[u];
                 v2[1] += (double)v[u] * (double)v[u];
-                dead += fabsf(v[u]) < 1e-6f ? 1 : 0;
+                dead += act_dead(v[u]) ? 1 : 0;
                 if (relu_inplace) x[(int64_t)(r + u) * cols + j] = v[u] > 0.0f ? v[u] : 0.0f;
             }
         }
@@ -2075,7 +2072,7 @@ __global__ __launch_bounds__(256) void k_act_stats_cols(float *__restrict__ x, i
             const float v = x[(int64_t)r * cols + j];
             v2[0] += (double)v;
             v2[1] += (double)v * (double)v;
-            dead += fabsf(v) < 1e-6f ? 1 : 0;
+            dead += act_dead(v) ? 1 : 0;
             if (relu_inplace) x[(int64_t)r * cols + j] = v > 0.0f ? v : 0.0f;
         }
     }
@@ -2114,12 +2111,7 @@ __global__ __launch_bounds__(64) void k_act_stats_final(const double *__restrict
         c += p[2];
         m = p[3] > m ? p[3] : m;
     }
-    const double n = (double)rows * (double)ls.cols[l];
-    const double var = (q - s * s / n) / (n - 1.0);
-    out[4 * l + 0] = s / n;
-    out[4 * l + 1] = sqrt(var > 0.0 ? var : 0.0);
-    out[4 * l + 2] = c / n;
-    out[4 * l + 3] = m / (double)rows;
+    act_quad(s, q, c, m, (double)rows * (double)ls.cols[l], (double)rows, out + 4 * l);
 }
 
 int validate_cnn_update(const gs_cnn_dims &dims, const gs_rollout_view_u8 &ro, int64_t B, const void *ws)
@@ -2238,11 +2230,7 @@ __global__ __launch_bounds__(256) void k_cnn_act_record(CnnActRec ar, int rows, 
     wg_reduce<2>(z, sred);
     if (tid == 0 && live) {
         const double n = (double)rows * (double)ar.neurons[l];
-        const double var = (z[1] - z[0] * z[0] / n) / (n - 1.0);
-        rec[GS_M_ACT + 4 * l + 0] = (float)(z[0] / n);
-        rec[GS_M_ACT + 4 * l + 1] = (float)sqrt(var > 0.0 ? var : 0.0);
-        rec[GS_M_ACT + 4 * l + 2] = (float)(v[0] / n);
-        rec[GS_M_ACT + 4 * l + 3] = (float)((double)smax / (double)rows);
+        act_quad(z[0], z[1], v[0], (double)smax, n, (double)rows, rec + GS_M_ACT + 4 * l);
     }
 }
 

@@ -146,6 +146,14 @@ constexpr int kMaxObsDim = 64;
 constexpr int kMaxHidden = 1024;
 constexpr int kMaxActions = 32;
 
+// the per-row kernels' compile-time action bound AMAX, 8 or 32 (gs_mlp1.hip, gs_pg.hip, gs_ppo_rows.hip)
+template <class F>
+int with_amax(int A, F &&f)
+{
+    if (A <= 8) return f(std::integral_constant<int, 8>{});
+    return f(std::integral_constant<int, 32>{});
+}
+
 // Workspace carve-up for one minibatch step (bytes, 256-aligned), see gs_ppo.hip.
 struct Workspace {
     float *x;        // (B, D)     gathered observations
@@ -492,11 +500,13 @@ struct ActOut {
     uint32_t *cnt;
     float *part;
 };
+constexpr float kDeadEps = 1e-6f;    // every path's dead test: a pre-activation value with |z| below this
+__device__ __forceinline__ bool act_dead(float z) { return fabsf(z) < kDeadEps; }
 __device__ __forceinline__ void act_acc(const ActOut &ao, float z, int64_t neuron, float &s, float &q)
 {
     s += z;
     q += z * z;
-    if (fabsf(z) < 1e-6f) atomicAdd(ao.cnt + neuron, 1u);
+    if (act_dead(z)) atomicAdd(ao.cnt + neuron, 1u);
 }
 // every lane of the wave calls it (the xor tree needs the whole wave); lane 0 writes the slot
 __device__ __forceinline__ void act_flush(const ActOut &ao, int64_t slot, float s, float q)

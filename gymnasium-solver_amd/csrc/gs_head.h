@@ -1,7 +1,7 @@
 // gs_head.h — the per-row arithmetic every policy's kernels share: the categorical head
 // (log-softmax statistics, action select, log-prob), one row of the PPO loss in pieces (the
-// categorical row, the PPO terms, their metric sums and analytic gradients), the metric record,
-// the fixed-order block sum, the clip coefficient and one parameter's Adam step.
+// categorical row, the PPO terms, their metric sums and analytic gradients), the metric record and
+// its tail, the fixed-order block sum, the clip coefficient and one parameter's Adam step.
 // Included by gs_mlp.hip (two hidden layers), gs_mlp1.hip (one hidden layer), gs_mc.hip, gs_cnn.hip
 // (NatureCNN: the PPO terms, the record and mix64 under its own masked head), gs_ppo_rows.hip (the
 // row-parallel PPO update: loss_row, write_metrics, block_reduce, clip_coef, adam_param) and, through
@@ -375,6 +375,37 @@ __device__ __forceinline__ bool write_metrics(const double *t, double Bd, const 
     metrics[GS_M_UNEVALUATED] = 0.0f;
     metrics[GS_M_RES1] = 0.0f;
     return kl_stop;
+}
+
+// the record of a minibatch after the sticky KL stop (never evaluated): every slot 0 but these three
+__device__ __forceinline__ float unevaluated_slot(int q)
+{
+    return (q == GS_M_SKIPPED || q == GS_M_KL_STOP || q == GS_M_UNEVALUATED) ? 1.0f : 0.0f;
+}
+
+// behind write_metrics in k_update1 and k_ppo_rows_step: the pre-clip norms, then zeros to the record's end
+__device__ __forceinline__ void write_step_tail(float *rec, float total, float gn_back, float gn_pol, float gn_val)
+{
+    rec[GS_M_GRAD_NORM] = total;
+    rec[GS_M_GN_BACKBONE] = gn_back;
+    rec[GS_M_GN_POLICY_HEAD] = gn_pol;
+    rec[GS_M_GN_VALUE_HEAD] = gn_val;
+    rec[GS_M_GN_MLP] = 0.0f;
+    for (int q = GS_M_RES20; q < GS_NUM_METRICS; ++q) rec[q] = 0.0f;
+}
+
+// A layer's GS_M_ACT quadruple out[4] = {mean, unbiased std, dead_pct, dead_max} (float in a record, double
+// for gs_cnn_activation_stats) from the double sums over its n = rows x neurons pre-activation values:
+// s1 = sum z, s2 = sum z^2, dead_sum / dead_max = the sum / the largest of the per-neuron act_dead counts
+template <class T>
+__device__ __forceinline__ void act_quad(double s1, double s2, double dead_sum, double dead_max, double n, double rows,
+                                         T *out)
+{
+    const double var = (s2 - s1 * s1 / n) / (n - 1.0);
+    out[0] = (T)(s1 / n);
+    out[1] = (T)sqrt(var > 0.0 ? var : 0.0);
+    out[2] = (T)(dead_sum / n);
+    out[3] = (T)(dead_max / rows);
 }
 
 }  // namespace gs

@@ -876,7 +876,7 @@ __device__ __forceinline__ void fwd_hidden_body(
                 }
                 sz += z;
                 sq += z * z;
-                dead += fabsf(z) < 1e-6f ? 1u : 0u;
+                dead += act_dead(z) ? 1u : 0u;
             }
             if (!have) sz = 0.0f, sq = 0.0f, dead = 0u;
 #pragma unroll
@@ -1399,12 +1399,8 @@ __global__ __launch_bounds__(256) void k_loss(const float *__restrict__ P, Layou
     if (la.step_base) metrics += *la.step_base * GS_NUM_METRICS;
     GS_STAMP_BEGIN(1)
     if (stop && *stop) {
-        if (tid == 0) {
-            for (int k = 0; k < GS_NUM_METRICS; ++k) metrics[k] = 0.0f;
-            metrics[GS_M_SKIPPED] = 1.0f;
-            metrics[GS_M_KL_STOP] = 1.0f;
-            metrics[GS_M_UNEVALUATED] = 1.0f;
-        }
+        if (tid == 0)
+            for (int k = 0; k < GS_NUM_METRICS; ++k) metrics[k] = unevaluated_slot(k);
         return;
     }
     const int A = L.A, A1 = A + 1;
@@ -3590,7 +3586,7 @@ __global__ __launch_bounds__(256) void k_mlp_act_stats(const float *__restrict__
             for (int d = 0; d < D; ++d) z = fmaf(P[L.oW1 + (int64_t)n * D + d], xs[r * D + d], z);
             st[0] += (double)z;
             st[1] += (double)z * (double)z;
-            cnt += fabsf(z) < 1e-6f ? 1 : 0;
+            cnt += act_dead(z) ? 1 : 0;
             h1s[r * H1 + n] = z > 0.0f ? z : 0.0f;
         }
         out[2 + n] = (double)cnt;
@@ -3614,7 +3610,7 @@ __global__ __launch_bounds__(256) void k_mlp_act_stats(const float *__restrict__
             if (r < nr) {
                 st2[0] += (double)z[r];
                 st2[1] += (double)z[r] * (double)z[r];
-                cnt += fabsf(z[r]) < 1e-6f ? 1 : 0;
+                cnt += act_dead(z[r]) ? 1 : 0;
             }
         out[2 + HM + 2 + n] = (double)cnt;
     }
@@ -3672,12 +3668,7 @@ __global__ __launch_bounds__(256) void k_act_parts_record(const double *__restri
 #pragma unroll
         for (int l = 0; l < 2; ++l) {
             const double n = (double)R * (double)(l == 0 ? H1 : H2);
-            const double s1 = zs[2 * l], s2 = zs[2 * l + 1];
-            const double var = (s2 - s1 * s1 / n) / (n - 1.0);
-            rec[4 * l + 0] = (float)(s1 / n);
-            rec[4 * l + 1] = (float)sqrt(var > 0.0 ? var : 0.0);
-            rec[4 * l + 2] = (float)(dsum[l] / n);
-            rec[4 * l + 3] = (float)((double)smax[l] / (double)R);
+            act_quad(zs[2 * l], zs[2 * l + 1], dsum[l], (double)smax[l], n, (double)R, rec + 4 * l);
         }
     }
 }
@@ -3886,12 +3877,7 @@ __global__ __launch_bounds__(256) void k_act_stats_fused(const uint32_t *__restr
 #pragma unroll
         for (int l = 0; l < 2; ++l) {
             const double H = l == 0 ? H1 : H2, n = (double)B * H;
-            const double s1 = zs[2 * l], s2 = zs[2 * l + 1];
-            const double var = (s2 - s1 * s1 / n) / (n - 1.0);
-            rec[4 * l + 0] = (float)(s1 / n);
-            rec[4 * l + 1] = (float)sqrt(var > 0.0 ? var : 0.0);
-            rec[4 * l + 2] = (float)(dsum[l] / n);
-            rec[4 * l + 3] = (float)((double)smax[l] / (double)B);
+            act_quad(zs[2 * l], zs[2 * l + 1], dsum[l], (double)smax[l], n, (double)B, rec + 4 * l);
         }
     }
 }

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
         __syncthreads();        // the previous step's parameters and stop decision
         if (s_stop) {           // sticky KL stop: never evaluated
             if (tid < GS_NUM_METRICS)
-                rec[tid] = (tid == GS_M_SKIPPED || tid == GS_M_KL_STOP || tid == GS_M_UNEVALUATED) ? 1.0f : 0.0f;
+                rec[tid] = unevaluated_slot(tid);
             continue;
         }
         const int32_t *idxk = a.idx + (int64_t)k * B;
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
                     if (a.act_stats) {
                         sz += (double)z;
                         sz2 += (double)z * (double)z;
-                        if (fabsf(z) < 1e-6f) atomicAdd(&dead[j], 1u);   // integer: order-free
+                        if (act_dead(z)) atomicAdd(&dead[j], 1u);   // integer: order-free
                     }
                     h = z > 0.0f ? z : 0.0f;
                 }
@@ -473,20 +473,9 @@ __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
         }
         if (tid == 0) {
             write_metrics(tot, rows, la, rec, true);
-            rec[GS_M_GRAD_NORM] = total;
-            rec[GS_M_GN_BACKBONE] = gn_back;
-            rec[GS_M_GN_POLICY_HEAD] = gn_pol;
-            rec[GS_M_GN_VALUE_HEAD] = gn_val;
-            rec[GS_M_GN_MLP] = 0.0f;
-            for (int q = GS_M_RES20; q < GS_NUM_METRICS; ++q) rec[q] = 0.0f;
-            if (a.act_stats) {
-                const double n = (double)B * (double)H;
-                const double var = (st[1] - st[0] * st[0] / n) / (n - 1.0);
-                rec[GS_M_ACT + 0] = (float)(st[0] / n);
-                rec[GS_M_ACT + 1] = (float)sqrt(var > 0.0 ? var : 0.0);
-                rec[GS_M_ACT + 2] = (float)(st[2] / n);
-                rec[GS_M_ACT + 3] = (float)((double)s_dead_max / (double)B);
-            }
+            write_step_tail(rec, total, gn_back, gn_pol, gn_val);
+            if (a.act_stats)
+                act_quad(st[0], st[1], st[2], (double)s_dead_max, (double)B * (double)H, (double)B, rec + GS_M_ACT);
             if (tripped) s_stop = 1;
         }
     }
@@ -531,20 +520,13 @@ __global__ __launch_bounds__(256) void k_act_stats1(const float *__restrict__ P,
             for (int d = 0; d < D; ++d) z = fmaf(P[L.oW1 + j * D + d], lds_x[r * D + d], z);
             st[0] += (double)z;
             st[1] += (double)z * (double)z;
-            cnt += fabsf(z) < 1e-6f ? 1 : 0;
+            cnt += act_dead(z) ? 1 : 0;
         }
         out[2 + j] = (double)cnt;
     }
     block_reduce<2>(st, sred);
     if (tid == 0) out[0] = st[0], out[1] = st[1];
     for (int j = tid; j < 2 + H; j += 256) out[2 + H + j] = 0.0;
-}
-
-template <class F>
-int with_amax(int A, F &&f)
-{
-    if (A <= 8) return f(std::integral_constant<int, 8>{});
-    return f(std::integral_constant<int, 32>{});
 }
 
 }  // namespace

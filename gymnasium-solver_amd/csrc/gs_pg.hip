@@ -17,15 +17,15 @@
 #include <math.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "gs_hparams.h"
 #include "gs_pg_head.h"
+#include "gs_rows.h"
 
 namespace gs {
 namespace {
 
-constexpr int R = kPgRows;
+constexpr int R = kRowsTile;
 
 struct PgRowArgs {
     const float *P;
@@ -51,11 +51,6 @@ struct PgStepArgs {
     float ent_coef;
     AdamArgs aa;
 };
-
-__device__ __forceinline__ int pg_sample(const int32_t *idx, int i, int TN)
-{
-    return min(max(idx[i], 0), TN - 1);      // an index outside the rollout is clamped, never followed
-}
 
 // out[r][j] = relu(b[j] + sum_k W[j][k] in[r][k]) for the tile's 16 rows; a thread owns one unit for
 // 4 rows, so a weight row is read once per 4 rows
@@ -116,16 +111,14 @@ __global__ void __launch_bounds__(256) k_pg_rows(Layout L, PgRowArgs a)
     if (a.normalize) {
         double v[2] = {0.0, 0.0};
         for (int i = tid; i < a.B; i += 256) {
-            const float t = a.targets[sample_row(pg_sample(a.idx, i, TN), a.T, a.N)];
+            const float t = a.targets[sample_row(rows_sample(a.idx, i, TN), a.T, a.N)];
             v[0] += (double)t;
             v[1] += (double)t * (double)t;
         }
         block_reduce<2, double>(v, red);
-        const double Bd = (double)a.B;
-        const double mean = v[0] / Bd;
-        const double var = fmax(0.0, (v[1] - v[0] * v[0] / Bd) / (Bd - 1.0));
-        tmean = (float)mean;
-        tden = (float)sqrt(var) + 1e-8f;
+        const RowsMoments m = rows_moments(v[0], v[1], (double)a.B);
+        tmean = (float)m.mean;
+        tden = (float)m.std + 1e-8f;
     }
 
     double acc[kPgSums];
@@ -139,9 +132,8 @@ __global__ void __launch_bounds__(256) k_pg_rows(Layout L, PgRowArgs a)
             int row = -1, act = 0;
             float t = 0.0f, olp = 0.0f;
             if (i < a.B) {
-                row = sample_row(pg_sample(a.idx, i, TN), a.T, a.N);
-                const int64_t ar = a.actions[row];
-                act = ar < 0 ? 0 : (ar >= A ? A - 1 : (int)ar);      // an action outside [0, A) is clamped
+                row = sample_row(rows_sample(a.idx, i, TN), a.T, a.N);
+                act = rows_action(a.actions[row], A);
                 t = a.targets[row];
                 if (a.normalize) t = (t - tmean) / tden;
                 olp = a.logprobs[row];
@@ -149,10 +141,7 @@ __global__ void __launch_bounds__(256) k_pg_rows(Layout L, PgRowArgs a)
             frow[tid] = row, fact[tid] = act, ft[tid] = t, folp[tid] = olp;
         }
         __syncthreads();
-        for (int e = tid; e < R * D; e += 256) {
-            const int r = e / D, d = e - r * D;
-            x[e] = frow[r] >= 0 ? a.obs[(size_t)frow[r] * D + d] : 0.0f;
-        }
+        rows_gather_obs(a.obs, frow, D, x);
         __syncthreads();
         pg_dense_relu(P + L.oW1, P + L.ob1, x, D, h1, H1);
         __syncthreads();
@@ -257,16 +246,7 @@ __global__ void __launch_bounds__(256) k_pg_rows(Layout L, PgRowArgs a)
         first = false;
         __syncthreads();
     }
-    // the workgroup's metric sums: its rows' accumulators added in row order
-    if (tid < R)
-#pragma unroll
-        for (int k = 0; k < kPgSums; ++k) rsum[tid * kPgSums + k] = acc[k];
-    __syncthreads();
-    if (tid < kPgSums) {
-        double s = 0.0;
-        for (int r = 0; r < R; ++r) s += rsum[r * kPgSums + tid];
-        a.msums[(size_t)blockIdx.x * kPgSums + tid] = s;
-    }
+    rows_store_sums(acc, rsum, a.msums + (size_t)blockIdx.x * kPgSums);
 }
 
 __global__ void __launch_bounds__(256) k_pg_step(Layout L, PgStepArgs a)
@@ -316,8 +296,8 @@ __global__ void __launch_bounds__(256) k_pg_step(Layout L, PgStepArgs a)
         for (int k = 0; k < GS_NUM_METRICS; ++k) m[k] = 0.0f;
         const float pl = (float)(-t[0] / Bd);
         const float ent = (float)(t[1] / Bd);
-        const float tm = (float)(t[4] / Bd);
-        const float ts = (float)sqrt(fmax(0.0, (t[5] - t[4] * t[4] / Bd) / (Bd - 1.0)));
+        const RowsMoments tgt = rows_moments(t[4], t[5], Bd);
+        const float tm = (float)tgt.mean, ts = (float)tgt.std;
         m[GS_M_LOSS] = pl + a.ent_coef * (-ent);
         m[GS_M_POLICY_LOSS] = pl;
         m[GS_M_ENTROPY] = ent;
@@ -348,21 +328,18 @@ struct PgWorkspace {
     size_t bytes;
 };
 
-size_t round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 PgWorkspace pg_carve(void *base, const Layout &L, int64_t B)
 {
     PgWorkspace w{};
     w.ntiles = (int)((B + R - 1) / R);
     w.groups = w.ntiles < kPgMaxGroups ? w.ntiles : kPgMaxGroups;
     w.stride = (int)((L.P + 3) & ~(int64_t)3);
-    char *p = (char *)base;
-    size_t o = 0;
-    w.ticket = (unsigned *)(p + o), o += 256;
-    w.normpart = (double *)(p + o), o += round256(sizeof(double) * 2 * kPgStepGroups);
-    w.msums = (double *)(p + o), o += round256(sizeof(double) * kPgSums * (size_t)w.groups);
-    w.slots = (float *)(p + o), o += round256(sizeof(float) * (size_t)w.groups * w.stride);
-    w.bytes = o;
+    RowsCarver c{(char *)base};
+    w.ticket = c.take<unsigned>(1);
+    w.normpart = c.take<double>(2 * kPgStepGroups);
+    w.msums = c.take<double>(kPgSums * (size_t)w.groups);
+    w.slots = c.take<float>((size_t)w.groups * w.stride);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -377,13 +354,6 @@ int pg_check_dims(const gs_mlp_dims &d)
     return GS_OK;
 }
 
-template <class F>
-int pg_with_amax(int A, F &&f)
-{
-    if (A <= 8) return f(std::integral_constant<int, 8>{});
-    return f(std::integral_constant<int, 32>{});
-}
-
 int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_mlp_dims &dims, const gs_pg_hparams &hp,
            const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n, int64_t adam_step0, float *metrics,
            void *workspace, size_t workspace_bytes, bool do_step, hipStream_t s, const char *what)
@@ -392,8 +362,7 @@ int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_m
     if (rc) return rc;
     GS_REQUIRE(!(hp.flags & GS_HP_BF16), "%s: precision bf16 is a mode of the PPO chain; the REINFORCE update is fp32 "
                                          "only", what);
-    GS_REQUIRE(batch >= 2 && batch <= (int64_t)1 << 20, "%s: batch %lld outside [2, 2^20]", what, (long long)batch);
-    GS_REQUIRE(ro.T > 0 && ro.N > 0 && ro.T * ro.N < (int64_t)1 << 31, "%s: rollout shape outside 1 <= T*N < 2^31", what);
+    if ((rc = rows_check_batch(batch, ro.T, ro.N, what))) return rc;
     GS_REQUIRE(ro.obs && ro.actions && ro.logprobs && ro.advantages,
                "%s: the rollout view needs obs, actions, logprobs and advantages (the policy targets)", what);
     GS_REQUIRE(n >= 0 && n < (int64_t)1 << 31 && adam_step0 >= 0, "%s: bad n_minibatches / adam_step0", what);
@@ -419,7 +388,7 @@ int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_m
         ra.normalize = hp.normalize_targets ? 1 : 0;
         ra.ent_coef = hp.ent_coef;
         ra.invB = 1.0f / (float)batch;
-        rc = pg_with_amax(L.A, [&](auto amax) {
+        rc = with_amax(L.A, [&](auto amax) {
             constexpr int AMAX = decltype(amax)::value;
             const int rl = set_lds_limit((const void *)k_pg_rows<AMAX>, lds);
             if (rl) return rl;
@@ -449,7 +418,7 @@ int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_m
 extern "C" size_t gs_pg_update_workspace_bytes(gs_mlp_dims dims, int64_t batch)
 {
     using namespace gs;
-    if (pg_check_dims(dims) != GS_OK || batch < 2 || batch > (int64_t)1 << 20) return 0;
+    if (pg_check_dims(dims) != GS_OK || !rows_batch_ok(batch)) return 0;
     return pg_carve(nullptr, Layout::make(dims.obs_dim, dims.hidden1, dims.hidden2, dims.n_actions), batch).bytes;
 }
 

@@ -10,7 +10,6 @@
 
 namespace gs {
 
-constexpr int kPgRows = 16;        // minibatch rows of one tile
 constexpr int kPgMaxGroups = 256;  // row workgroups (and partial slots) at most: the MI355X's CU count
 constexpr int kPgMaxHidden = 512;
 constexpr int kPgStepGroups = 64;  // step workgroups at most

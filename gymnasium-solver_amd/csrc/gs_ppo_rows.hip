@@ -32,15 +32,15 @@
 #include <math.h>
 
 #include <algorithm>
-#include <type_traits>
 
 #include "gs_head.h"
 #include "gs_hparams.h"
+#include "gs_rows.h"
 
 namespace gs {
 namespace {
 
-constexpr int R = 16;                  // minibatch rows of one tile: one MFMA row block
+constexpr int R = kRowsTile;
 constexpr int kRowsMaxGroups = 256;    // row workgroups (and partial slots) at most: the MI355X's CU count
 constexpr int kRowsMaxHidden = 512;
 constexpr int kRowsSumGroups = 256;    // workgroups of the sum and step kernels at most
@@ -108,11 +108,6 @@ struct RowsStepArgs {
     AdamArgs aa;
 };
 
-__device__ __forceinline__ int rows_sample(const int32_t *idx, int i, int TN)
-{
-    return min(max(idx[i], 0), TN - 1);      // an index outside the rollout is clamped, never followed
-}
-
 __host__ __device__ inline size_t rows_lds_bytes(const RowsLayout &L)
 {
     const size_t A1 = L.A + 1;
@@ -161,7 +156,7 @@ __device__ __forceinline__ void rows_layer1(const float *__restrict__ W, const f
             if (stats && frow[4 * rb + i] >= 0) {
                 st[0] += (double)a[i];
                 st[1] += (double)a[i] * (double)a[i];
-                if (fabsf(a[i]) < 1e-6f) atomicAdd(&cnt[j], 1u);     // integer: order-free
+                if (act_dead(a[i])) atomicAdd(&cnt[j], 1u);     // integer: order-free
             }
             out[(size_t)(4 * rb + i) * S + j] = fmaxf(a[i], 0.0f);
         }
@@ -202,10 +197,9 @@ __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
     if (la.normalize) {
         double s0 = 0.0, s1 = 0.0;
         for (int w = 0; w < a.nparts; ++w) s0 += a.advparts[2 * w], s1 += a.advparts[2 * w + 1];
-        const double Bd = (double)a.B;
-        const double var = fmax(0.0, (s1 - s0 * s0 / Bd) / (Bd - 1.0));
-        amean = (float)(s0 / Bd);
-        aden = (float)sqrt(var) + 1e-8f;
+        const RowsMoments m = rows_moments(s0, s1, (double)a.B);
+        amean = (float)m.mean;
+        aden = (float)m.std + 1e-8f;
     }
     if (stats)
         for (int j = tid; j < H1 + H2; j += 256) dead[j] = 0u;
@@ -223,8 +217,7 @@ __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
             float adv = 0.0f, olp = 0.0f, ov = 0.0f, ret = 0.0f;
             if (i < a.B) {
                 row = sample_row(rows_sample(a.idx, i, TN), a.T, a.N);
-                const int64_t ar = a.actions[row];
-                act = ar < 0 ? 0 : (ar >= A ? A - 1 : (int)ar);      // an action outside [0, A) is clamped
+                act = rows_action(a.actions[row], A);
                 adv = a.advantages[row];
                 if (la.normalize) adv = (adv - amean) / aden;
                 olp = a.logprobs[row], ov = a.values[row], ret = a.returns[row];
@@ -232,10 +225,7 @@ __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
             frow[tid] = row, fact[tid] = act, fadv[tid] = adv, folp[tid] = olp, fov[tid] = ov, fret[tid] = ret;
         }
         __syncthreads();
-        for (int e = tid; e < R * D; e += 256) {
-            const int r = e / D, d = e - r * D;
-            x[e] = frow[r] >= 0 ? a.obs[(size_t)frow[r] * D + d] : 0.0f;
-        }
+        rows_gather_obs(a.obs, frow, D, x);
         __syncthreads();
         rows_layer1(P + L.oW1, P + L.ob1, x, D, h1, H1, S1, frow, stats, st, dead);
         __syncthreads();
@@ -281,7 +271,7 @@ __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
                     if (stats && frow[r] >= 0) {
                         st[2] += (double)zz;
                         st[3] += (double)zz * (double)zz;
-                        if (fabsf(zz) < 1e-6f) atomicAdd(&dead[H1 + j0 + ln], 1u);
+                        if (act_dead(zz)) atomicAdd(&dead[H1 + j0 + ln], 1u);
                     }
                     h2[r * S2 + j0 + ln] = fmaxf(zz, 0.0f);
                 }
@@ -452,16 +442,7 @@ __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
         first = false;
         __syncthreads();
     }
-    // the workgroup's metric sums: its rows' accumulators added in row order
-    if (tid < R)
-#pragma unroll
-        for (int k = 0; k < kNumSums; ++k) rsum[tid * kNumSums + k] = acc[k];
-    __syncthreads();
-    if (tid < kNumSums) {
-        double s = 0.0;
-        for (int r = 0; r < R; ++r) s += rsum[r * kNumSums + tid];
-        a.msums[(size_t)blockIdx.x * kNumSums + tid] = s;
-    }
+    rows_store_sums(acc, rsum, a.msums + (size_t)blockIdx.x * kNumSums);
     if (stats) {
         block_reduce<4, double>(st, red);
         if (tid < 4) a.actsums[(size_t)blockIdx.x * 4 + tid] = st[tid];
@@ -511,8 +492,7 @@ __global__ void __launch_bounds__(256) k_ppo_rows_step(RowsLayout L, RowsStepArg
     const int tid = threadIdx.x;
     float *rec = a.metrics;
     if (a.stop && *a.stop != 0) {    // stopped before this step: never evaluated
-        if (blockIdx.x == 0 && tid < GS_NUM_METRICS)
-            rec[tid] = (tid == GS_M_SKIPPED || tid == GS_M_KL_STOP || tid == GS_M_UNEVALUATED) ? 1.0f : 0.0f;
+        if (blockIdx.x == 0 && tid < GS_NUM_METRICS) rec[tid] = unevaluated_slot(tid);
         return;
     }
     if (tid == 0) s_trip = a.stop && rows_tripped(a.msums, a.groups, a.B, a.la.target_kl) ? 1 : 0;
@@ -553,21 +533,14 @@ __global__ void __launch_bounds__(256) k_ppo_rows_step(RowsLayout L, RowsStepArg
     const float total = tripped ? 0.0f : (float)sqrt(nrm[0] + nrm[1] + nrm[2]);
     if (blockIdx.x == 0 && tid == 0) {
         write_metrics(tot, (double)a.B, a.la, rec, true);
-        rec[GS_M_GRAD_NORM] = total;
-        rec[GS_M_GN_BACKBONE] = tripped ? 0.0f : (float)sqrt(nrm[0]);
-        rec[GS_M_GN_POLICY_HEAD] = tripped ? 0.0f : (float)sqrt(nrm[1]);
-        rec[GS_M_GN_VALUE_HEAD] = tripped ? 0.0f : (float)sqrt(nrm[2]);
-        rec[GS_M_GN_MLP] = 0.0f;
-        for (int q = GS_M_RES20; q < GS_NUM_METRICS; ++q) rec[q] = 0.0f;
+        write_step_tail(rec, total, tripped ? 0.0f : (float)sqrt(nrm[0]), tripped ? 0.0f : (float)sqrt(nrm[1]),
+                        tripped ? 0.0f : (float)sqrt(nrm[2]));
         if (a.act_stats) {
             const int nl = L.two ? 2 : 1;
             for (int l = 0; l < nl; ++l) {
                 const double n = (double)a.B * (double)(l ? L.H2 : L.H1);
-                const double var = (ast[2 * l + 1] - ast[2 * l] * ast[2 * l] / n) / (n - 1.0);
-                rec[GS_M_ACT + 4 * l + 0] = (float)(ast[2 * l] / n);
-                rec[GS_M_ACT + 4 * l + 1] = (float)sqrt(var > 0.0 ? var : 0.0);
-                rec[GS_M_ACT + 4 * l + 2] = (float)((double)cnt[2 * l] / n);
-                rec[GS_M_ACT + 4 * l + 3] = (float)((double)cnt[2 * l + 1] / (double)a.B);
+                act_quad(ast[2 * l], ast[2 * l + 1], (double)cnt[2 * l], (double)cnt[2 * l + 1], n, (double)a.B,
+                         rec + GS_M_ACT + 4 * l);
             }
         }
         if (tripped) *a.stop = 1;    // the other workgroups return below whichever value they read
@@ -590,8 +563,6 @@ struct RowsWorkspace {
     size_t bytes;
 };
 
-size_t rows_round256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 RowsWorkspace rows_carve(void *base, const RowsLayout &L, int64_t B)
 {
     RowsWorkspace w{};
@@ -601,15 +572,14 @@ RowsWorkspace rows_carve(void *base, const RowsLayout &L, int64_t B)
     w.nparts = (int)std::min<int64_t>(kRowsAdvParts, (B + 255) / 256);
     w.chunk = (int)((B + w.nparts - 1) / w.nparts);
     w.nsum = std::min(kRowsSumGroups, (L.P + 255) / 256);
-    char *p = (char *)base;
-    size_t o = 0;
-    w.advparts = (double *)(p + o), o += rows_round256(sizeof(double) * 2 * kRowsAdvParts);
-    w.normparts = (double *)(p + o), o += rows_round256(sizeof(double) * 3 * kRowsSumGroups);
-    w.msums = (double *)(p + o), o += rows_round256(sizeof(double) * kNumSums * (size_t)w.groups);
-    w.actsums = (double *)(p + o), o += rows_round256(sizeof(double) * 4 * (size_t)w.groups);
-    w.dead = (uint32_t *)(p + o), o += rows_round256(sizeof(uint32_t) * (size_t)(L.H1 + L.H2) * w.groups);
-    w.slots = (float *)(p + o), o += rows_round256(sizeof(float) * (size_t)w.groups * w.stride);
-    w.bytes = o;
+    RowsCarver c{(char *)base};
+    w.advparts = c.take<double>(2 * kRowsAdvParts);
+    w.normparts = c.take<double>(3 * kRowsSumGroups);
+    w.msums = c.take<double>(kNumSums * (size_t)w.groups);
+    w.actsums = c.take<double>(4 * (size_t)w.groups);
+    w.dead = c.take<uint32_t>((size_t)(L.H1 + L.H2) * w.groups);
+    w.slots = c.take<float>((size_t)w.groups * w.stride);
+    w.bytes = c.bytes;
     return w;
 }
 
@@ -626,17 +596,10 @@ int rows_check_dims(const gs_mlp_dims &d, const char *what)
     return GS_OK;
 }
 
-bool rows_batch_ok(int64_t batch) { return batch >= 2 && batch <= (int64_t)1 << 20; }
-
 template <class F>
 int rows_dispatch(const RowsLayout &L, F &&f)
 {
-    if (L.two) {
-        if (L.A <= 8) return f(std::integral_constant<int, 8>{}, std::true_type{});
-        return f(std::integral_constant<int, 32>{}, std::true_type{});
-    }
-    if (L.A <= 8) return f(std::integral_constant<int, 8>{}, std::false_type{});
-    return f(std::integral_constant<int, 32>{}, std::false_type{});
+    return with_amax(L.A, [&](auto amax) { return L.two ? f(amax, std::true_type{}) : f(amax, std::false_type{}); });
 }
 
 int rows_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_mlp_dims &dims, const gs_ppo_hparams &hp,
@@ -647,8 +610,7 @@ int rows_run(float *params, float *grads, float *adam_m, float *adam_v, const gs
     if (rc) return rc;
     GS_REQUIRE(!(hp.flags & GS_HP_BF16), "%s: precision bf16 is a mode of the fused chain; the row-parallel update is "
                                          "fp32 only", what);
-    GS_REQUIRE(rows_batch_ok(batch), "%s: batch %lld outside [2, 2^20]", what, (long long)batch);
-    GS_REQUIRE(ro.T > 0 && ro.N > 0 && ro.T * ro.N < (int64_t)1 << 31, "%s: rollout shape outside 1 <= T*N < 2^31", what);
+    if ((rc = rows_check_batch(batch, ro.T, ro.N, what))) return rc;
     const RowsLayout L = rows_layout(dims);
     const RowsWorkspace ws = rows_carve(workspace, L, batch);
     GS_REQUIRE(workspace_bytes >= ws.bytes, "%s: workspace of %zu bytes, gs_ppo_rows_workspace_bytes asks for %zu", what,
