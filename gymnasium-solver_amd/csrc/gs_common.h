@@ -334,7 +334,7 @@ int launch_fwd_hidden(const float *params, const Layout &L, const float *obs, co
 size_t fwd_lds_bytes(const Layout &L);
 int launch_heads_act(const float *P, const Layout &L, const float *zpart, int64_t rows, int mode, uint64_t seed,
                      uint64_t counter, int64_t *actions, float *logp, float *value, hipStream_t s,
-                     const uint64_t *clock = nullptr);
+                     const uint64_t *clock = nullptr, uint32_t valid_mask = 0u);    // 0: the unmasked head
 int launch_loss(const float *P, const Layout &L, int64_t B, const Workspace &ws, const LossArgs &la, float *metrics,
                 int32_t *stop, hipStream_t s);
 // nt: threads per workgroup (512: the single-GPU chain entry's eight waves keep more partial tiles)
@@ -412,7 +412,7 @@ int mlp1_check_dims(const gs_mlp_dims &d);
 size_t mlp1_update_lds_bytes(const gs_mlp_dims &d);
 int mlp1_policy_act(const float *params, const gs_mlp_dims &d, const float *obs, int64_t N, int mode, uint64_t rng_seed,
                     uint64_t rng_counter, int64_t *actions, float *logp, float *value, float *obs_store,
-                    const uint64_t *clock, hipStream_t s);
+                    const uint64_t *clock, hipStream_t s, uint32_t valid_mask = 0u);    // 0: the unmasked head
 int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const gs_mlp_dims &d,
                 const gs_ppo_hparams &hp, const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n,
                 int64_t adam_step0, float *metrics, int32_t *stop_flag, bool loss_only, hipStream_t s);

@@ -341,6 +341,179 @@ __device__ __forceinline__ void loss_row(const float (&z)[AMAX + 1], int A, int 
     dzr[A] = ppo_row_dvalue(t, la, invB);
 }
 
+// ------------------------------------------------------------------------------------
+// The masked head of the MLP policies (MaskedCategorical, utils/distributions.py:8-82; the policy is
+// built with valid_actions = spec.action_space.valid, utils/models.py:285-346): the counterparts of
+// head_stats / head_act_row / cat_row / cat_row_grad / loss_row over the valid actions only.
+// valid: bit a set = action a valid, never 0 here (the entries send a zero mask to the functions
+// above).  The mask is uniform over the grid, so an invalid action costs a scalar branch: its
+// exponentials are never formed.  The act works on the row's logits in registers (head_stats_masked,
+// head_act_row_masked), the loss row on the logits in memory (cat_row_masked and what follows it).
+// The semantics are gs_cnn.hip's (mrow_stats, act_select, cnn_loss_row).
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ bool head_valid(uint32_t valid, int a, int A) { return a < A && ((valid >> a) & 1u) != 0u; }
+
+template <int AMAX>
+__device__ __forceinline__ HeadRow head_stats_masked(const float (&z)[AMAX + 1], int A, uint32_t valid)
+{
+    float m = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+        if (head_valid(valid, a, A)) m = fmaxf(m, z[a]);
+    float se = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+        if (head_valid(valid, a, A)) se += expf(z[a] - m);
+    HeadRow h;
+    h.lse = m + logf(se);
+    float m2 = -INFINITY;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+        if (head_valid(valid, a, A)) m2 = fmaxf(m2, z[a] - h.lse);
+    h.m2 = m2;
+    float S = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+        if (head_valid(valid, a, A)) S += expf((z[a] - h.lse) - m2);
+    h.S = S;
+    return h;
+}
+
+// head_act_row over the valid actions: mode 1 takes the first maximum among them, mode 0 runs the
+// inverse CDF over them in index order under the same counter-based uniform (the fallback is the last
+// valid action), mode 2 replays the recorded action (one outside the valid set is the caller's error:
+// its log-prob is unspecified, and nothing is read out of range)
+template <int AMAX>
+__device__ __forceinline__ void head_act_row_masked(const float (&z)[AMAX + 1], int A, uint32_t valid, int mode,
+                                                    uint64_t seed, uint64_t ctr, int64_t r,
+                                                    int64_t *__restrict__ action, float *__restrict__ logp,
+                                                    float *__restrict__ value)
+{
+    float v = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AMAX + 1; ++a)
+        if (a == A) v = z[a];
+    if (value) *value = v;
+    if (!action) return;
+    const HeadRow h = head_stats_masked<AMAX>(z, A, valid);
+    int act = -1;
+    if (mode == 2) {
+        act = (int)*action;
+    } else if (mode == 1) {
+        float best = -INFINITY;
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a) {
+            if (head_valid(valid, a, A)) {
+                const float p = expf((z[a] - h.lse) - h.m2) / h.S;
+                if (p > best) { best = p; act = a; }
+            }
+        }
+        *action = act;
+    } else {
+        const uint64_t hh = mix64(mix64(mix64(seed) ^ ctr) ^ (uint64_t)r);
+        const float u = (float)(hh >> 40) * (1.0f / 16777216.0f);
+        float c = 0.0f;
+        int last = 0;
+#pragma unroll
+        for (int a = 0; a < AMAX; ++a) {
+            if (head_valid(valid, a, A)) {
+                last = a;
+                c += expf((z[a] - h.lse) - h.m2) / h.S;
+                if (act < 0 && u < c) act = a;
+            }
+        }
+        if (act < 0) act = last;
+        *action = act;
+    }
+    float za = 0.0f;
+#pragma unroll
+    for (int a = 0; a < AMAX; ++a)
+        if (a == act) za = z[a];
+    *logp = za - h.lse;
+}
+
+// The masked categorical row of a loss.  Unlike cat_row it reads the logits from memory (z: the row's
+// logits | value, in LDS in k_ppo_rows) and walks the mask's set bits in index order, so it touches
+// the valid actions only and holds no per-action array: with 3 of 18 actions valid the row forms 3
+// exponentials per pass where an unrolled 32-action form held ~100 registers live across the row
+// and measured 6 % slower per optimizer step than the unmasked kernel.
+// p = softmax over the valid actions, lp = z[act] - lse_valid (0 for an action outside the set),
+// H = -sum_valid p logf(p + 1e-8f) (MaskedCategorical.entropy, not Categorical's clamp form), and what
+// its gradient needs: g_a = logf(p_a + 1e-8f) + p_a / (p_a + 1e-8f) (= -dH/dp_a), pg = sum_b p_b g_b.
+struct MaskedCatRow {
+    float lse, m2, invS;       // head_stats over the valid actions
+    float H, lp, pg;
+};
+
+// one valid action's terms, formed alike by the row and by its gradient
+struct MaskedTerm { float ln, p, g, plq; };
+__device__ __forceinline__ MaskedTerm masked_term(float za, const MaskedCatRow &c)
+{
+    MaskedTerm t;
+    t.ln = za - c.lse;
+    t.p = expf(t.ln - c.m2) * c.invS;
+    const float lq = logf(t.p + 1e-8f);
+    t.g = lq + t.p / (t.p + 1e-8f);
+    t.plq = t.p * lq;
+    return t;
+}
+
+__device__ __forceinline__ MaskedCatRow cat_row_masked(const float *__restrict__ z, uint32_t valid, int act)
+{
+    float m = -INFINITY;
+    for (uint32_t b = valid; b; b &= b - 1u) m = fmaxf(m, z[__builtin_ctz(b)]);
+    float se = 0.0f;
+    for (uint32_t b = valid; b; b &= b - 1u) se += expf(z[__builtin_ctz(b)] - m);
+    MaskedCatRow c;
+    c.lse = m + logf(se);
+    float m2 = -INFINITY;
+    for (uint32_t b = valid; b; b &= b - 1u) m2 = fmaxf(m2, z[__builtin_ctz(b)] - c.lse);
+    c.m2 = m2;
+    float S = 0.0f;
+    for (uint32_t b = valid; b; b &= b - 1u) S += expf((z[__builtin_ctz(b)] - c.lse) - m2);
+    c.invS = 1.0f / S;
+    float H = 0.0f, lp = 0.0f, pg = 0.0f;
+    for (uint32_t b = valid; b; b &= b - 1u) {
+        const int a = __builtin_ctz(b);
+        const MaskedTerm t = masked_term(z[a], c);
+        H += t.plq;
+        pg += t.p * t.g;
+        if (a == act) lp = t.ln;
+    }
+    c.H = -H;
+    c.lp = lp;
+    c.pg = pg;
+    return c;
+}
+
+// dLoss/dlogits of a masked row: dH/dz_a = -p_a (g_a - pg); exactly 0 for an invalid action
+// (masked_fill blocks its gradient), so the invalid rows of the policy head never move
+__device__ __forceinline__ void cat_row_grad_masked(const float *__restrict__ z, const MaskedCatRow &c, int A,
+                                                    uint32_t valid, int act, float dlp, float dH,
+                                                    float *__restrict__ dzr)
+{
+    for (int a = 0; a < A; ++a) dzr[a] = 0.0f;
+    for (uint32_t b = valid; b; b &= b - 1u) {
+        const int a = __builtin_ctz(b);
+        const MaskedTerm t = masked_term(z[a], c);
+        const float pe = expf(t.ln);   // softmax(z) as seen by logsumexp backward
+        dzr[a] = dlp * ((a == act ? 1.0f : 0.0f) - pe) + dH * (t.p * (c.pg - t.g));
+    }
+}
+
+// loss_row under a mask; z[A] = the value.  Every set bit of valid is below A (the entries check)
+__device__ __forceinline__ void loss_row_masked(const float *__restrict__ z, int A, uint32_t valid, int act, float olp,
+                                                float ov, float adv, float ret, const LossArgs &la, float invB,
+                                                float *__restrict__ dzr, double (&acc)[kNumSums])
+{
+    const float v = z[A];
+    const MaskedCatRow c = cat_row_masked(z, valid, act);
+    const PpoRowTerms t = ppo_row_terms(c.lp, olp, v, ov, adv, ret, la);
+    ppo_row_sums(t, c.H, c.lp, olp, v, adv, ret, la, acc);
+    cat_row_grad_masked(z, c, A, valid, act, ppo_row_dlp(t, adv, la, invB), -la.ent_coef * invB, dzr);
+    dzr[A] = ppo_row_dvalue(t, la, invB);
+}
+
 // metrics record from the sums 0..12 (shared by k_loss, the fused path's k_metrics_all, the
 // one-hidden-layer update and the NatureCNN's cnn_write_metrics); GS_M_GRAD_NORM is the caller's.
 // Returns whether approx_kl passed target_kl (the KL early stop)

@@ -1056,14 +1056,15 @@ __device__ __forceinline__ void gather_head_row(const float *__restrict__ zpart,
 
 // ------------------------------------------------------------------------------------
 // k_heads_act: rollout head — logits/value from partials, action select, log_prob
-// (head_act_row, gs_head.h).  one thread per env row.
+// (head_act_row, gs_head.h).  one thread per env row.  MASKED: head_act_row_masked over `valid`
+// (gs_policy_act_masked); the unmasked kernel never reads its last argument.
 // ------------------------------------------------------------------------------------
-template <class S>
+template <class S, bool MASKED>
 __global__ __launch_bounds__(256) void k_heads_act(const float *__restrict__ P, Layout Lrt,
                                                    const float *__restrict__ zpart, int64_t rows, int mode,
                                                    uint64_t seed, uint64_t counter, int64_t *__restrict__ actions,
                                                    float *__restrict__ logp, float *__restrict__ value,
-                                                   const uint64_t *__restrict__ clock)
+                                                   const uint64_t *__restrict__ clock, uint32_t valid)
 {
     constexpr int AMAX = S::AMAX, AEX = S::AEX;
     const Layout L = S::lay(Lrt);
@@ -1072,8 +1073,12 @@ __global__ __launch_bounds__(256) void k_heads_act(const float *__restrict__ P, 
     float z[AMAX + 1];
     gather_head_row<AMAX, AEX>(zpart, P, L, r, z);
     const uint64_t ctr = counter + (clock && mode == 0 ? clock[0] : 0ull);   // rollout clock (graph replay)
-    head_act_row<AMAX>(z, L.A, mode, seed, ctr, r, actions ? actions + r : nullptr, logp ? logp + r : nullptr,
-                       value ? value + r : nullptr);
+    if constexpr (MASKED)
+        head_act_row_masked<AMAX>(z, L.A, valid, mode, seed, ctr, r, actions ? actions + r : nullptr,
+                                  logp ? logp + r : nullptr, value ? value + r : nullptr);
+    else
+        head_act_row<AMAX>(z, L.A, mode, seed, ctr, r, actions ? actions + r : nullptr, logp ? logp + r : nullptr,
+                           value ? value + r : nullptr);
 }
 
 // ------------------------------------------------------------------------------------
@@ -3136,12 +3141,16 @@ int prepare_kernels(const Layout &L, int64_t B)
 
 int launch_heads_act(const float *P, const Layout &L, const float *zpart, int64_t rows, int mode, uint64_t seed,
                      uint64_t counter, int64_t *actions, float *logp, float *value, hipStream_t s,
-                     const uint64_t *clock)
+                     const uint64_t *clock, uint32_t valid_mask)
 {
     const dim3 grid((unsigned)((rows + 255) / 256));
     return with_shape(L, 0, [&](auto sh) {
-        hipLaunchKernelGGL(k_heads_act<decltype(sh)>, grid, dim3(256), 0, s, P, L, zpart, rows, mode, seed, counter,
-                           actions, logp, value, clock);
+        if (valid_mask != 0u)
+            hipLaunchKernelGGL((k_heads_act<decltype(sh), true>), grid, dim3(256), 0, s, P, L, zpart, rows, mode, seed,
+                               counter, actions, logp, value, clock, valid_mask);
+        else
+            hipLaunchKernelGGL((k_heads_act<decltype(sh), false>), grid, dim3(256), 0, s, P, L, zpart, rows, mode, seed,
+                               counter, actions, logp, value, clock, 0u);
         GS_LAUNCH_CHECK("k_heads_act");
         return GS_OK;
     });

@@ -137,13 +137,15 @@ __device__ __forceinline__ void mlp1_forward_row(const float *Ps, const Layout1 
 // ------------------------------------------------------------------------------------
 // k_act1: rollout step / value forward, one thread per env row, 256 rows per workgroup.
 // LDS (floats): Ps[round4(P)] xs[256][D | 1]
+// MASKED: head_act_row_masked over `valid` (gs_policy_act_masked); the unmasked kernel never reads
+// its last argument.
 // ------------------------------------------------------------------------------------
-template <int AMAX>
+template <int AMAX, bool MASKED>
 __global__ __launch_bounds__(256) void k_act1(const float *__restrict__ P, Layout1 L, const float *__restrict__ obs,
                                               int64_t N, int mode, uint64_t seed, uint64_t counter,
                                               int64_t *__restrict__ actions, float *__restrict__ logp,
                                               float *__restrict__ value, float *__restrict__ obs_store,
-                                              const uint64_t *__restrict__ clock)
+                                              const uint64_t *__restrict__ clock, uint32_t valid)
 {
     extern __shared__ float lds_f[];
     float *Ps = lds_f;
@@ -164,8 +166,12 @@ __global__ __launch_bounds__(256) void k_act1(const float *__restrict__ P, Layou
     mlp1_forward_row<AMAX>(Ps, L, xs + tid * Dp, z);
     const int64_t r = row0 + tid;
     const uint64_t ctr = counter + (clock && mode == 0 ? clock[0] : 0ull);   // rollout clock (graph replay)
-    head_act_row<AMAX>(z, A, mode, seed, ctr, r, actions ? actions + r : nullptr, logp ? logp + r : nullptr,
-                       value ? value + r : nullptr);
+    if constexpr (MASKED)
+        head_act_row_masked<AMAX>(z, A, valid, mode, seed, ctr, r, actions ? actions + r : nullptr,
+                                  logp ? logp + r : nullptr, value ? value + r : nullptr);
+    else
+        head_act_row<AMAX>(z, A, mode, seed, ctr, r, actions ? actions + r : nullptr, logp ? logp + r : nullptr,
+                           value ? value + r : nullptr);
 }
 
 // ------------------------------------------------------------------------------------
@@ -554,7 +560,7 @@ int mlp1_check_dims(const gs_mlp_dims &d)
 
 int mlp1_policy_act(const float *params, const gs_mlp_dims &d, const float *obs, int64_t N, int mode, uint64_t rng_seed,
                     uint64_t rng_counter, int64_t *actions, float *logp, float *value, float *obs_store,
-                    const uint64_t *clock, hipStream_t s)
+                    const uint64_t *clock, hipStream_t s, uint32_t valid_mask)
 {
     int rc = mlp1_check_dims(d);
     if (rc) return rc;
@@ -566,12 +572,16 @@ int mlp1_policy_act(const float *params, const gs_mlp_dims &d, const float *obs,
     const unsigned nb = (unsigned)((N + 255) / 256);
     return with_amax(L.A, [&](auto amax) {
         constexpr int AMAX = decltype(amax)::value;
-        const int rl = set_lds_limit((const void *)k_act1<AMAX>, lds);
-        if (rl) return rl;
-        hipLaunchKernelGGL(k_act1<AMAX>, dim3(nb), dim3(256), lds, s, params, L, obs, N, mode, rng_seed, rng_counter,
-                           actions, logp, value, obs_store, clock);
-        GS_LAUNCH_CHECK("k_act1");
-        return (int)GS_OK;
+        auto launch = [&](auto masked) {
+            constexpr bool MASKED = decltype(masked)::value;
+            const int rl = set_lds_limit((const void *)k_act1<AMAX, MASKED>, lds);
+            if (rl) return rl;
+            hipLaunchKernelGGL((k_act1<AMAX, MASKED>), dim3(nb), dim3(256), lds, s, params, L, obs, N, mode, rng_seed,
+                               rng_counter, actions, logp, value, obs_store, clock, valid_mask);
+            GS_LAUNCH_CHECK("k_act1");
+            return (int)GS_OK;
+        };
+        return valid_mask != 0u ? launch(std::true_type{}) : launch(std::false_type{});
     });
 }
 

@@ -111,28 +111,50 @@ extern "C" size_t gs_policy_scratch_bytes(gs_mlp_dims dims, int64_t N)
     return align256((size_t)n_col_blocks(L.H2) * N * (L.A + 1) * sizeof(float));
 }
 
-extern "C" int gs_policy_act(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, int mode,
-                             uint64_t rng_seed, uint64_t rng_counter, int64_t *actions, float *logp, float *value,
-                             float *obs_store, void *scratch, const uint64_t *clock, void *stream)
+// gs_policy_act (valid_mask 0) and gs_policy_act_masked under the entry's name: the same launches, the
+// head kernel taking head_act_row or head_act_row_masked
+static int policy_act(const char *who, const float *params, gs_mlp_dims dims, const float *obs, int64_t N, int mode,
+                      uint64_t rng_seed, uint64_t rng_counter, int64_t *actions, float *logp, float *value,
+                      float *obs_store, void *scratch, const uint64_t *clock, void *stream, uint32_t valid_mask)
 {
     if (one_layer(dims)) {
-        GS_REQUIRE(actions && logp && value, "gs_policy_act: null buffer");
+        GS_REQUIRE(actions && logp && value, "%s: null buffer", who);
         return mlp1_policy_act(params, dims, obs, N, mode, rng_seed, rng_counter, actions, logp, value, obs_store,
-                               clock, (hipStream_t)stream);
+                               clock, (hipStream_t)stream, valid_mask);
     }
     int rc = check_dims(dims);
     if (rc) return rc;
-    GS_REQUIRE(N > 0, "gs_policy_act: N must be > 0");
-    GS_REQUIRE(mode >= 0 && mode <= 2, "gs_policy_act: mode %d not in {0,1,2}", mode);
-    GS_REQUIRE(params && obs && actions && logp && value && scratch, "gs_policy_act: null buffer");
-    GS_REQUIRE(((uintptr_t)scratch & 15) == 0, "gs_policy_act: scratch must be 16-byte aligned");
+    GS_REQUIRE(N > 0, "%s: N must be > 0", who);
+    GS_REQUIRE(mode >= 0 && mode <= 2, "%s: mode %d not in {0,1,2}", who, mode);
+    GS_REQUIRE(params && obs && actions && logp && value && scratch, "%s: null buffer", who);
+    GS_REQUIRE(((uintptr_t)scratch & 15) == 0, "%s: scratch must be 16-byte aligned", who);
     const Layout L = layout_of(dims);
     hipStream_t s = (hipStream_t)stream;
     float *zpart = (float *)scratch;
     rc = launch_fwd_hidden(params, L, obs, nullptr, 1, N, N, nullptr, nullptr, nullptr, zpart, obs_store, nullptr,
                            nullptr, s);
     if (rc) return rc;
-    return launch_heads_act(params, L, zpart, N, mode, rng_seed, rng_counter, actions, logp, value, s, clock);
+    return launch_heads_act(params, L, zpart, N, mode, rng_seed, rng_counter, actions, logp, value, s, clock, valid_mask);
+}
+
+extern "C" int gs_policy_act(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, int mode,
+                             uint64_t rng_seed, uint64_t rng_counter, int64_t *actions, float *logp, float *value,
+                             float *obs_store, void *scratch, const uint64_t *clock, void *stream)
+{
+    return policy_act("gs_policy_act", params, dims, obs, N, mode, rng_seed, rng_counter, actions, logp, value, obs_store,
+                      scratch, clock, stream, 0u);
+}
+
+extern "C" int gs_policy_act_masked(const float *params, gs_mlp_dims dims, const float *obs, int64_t N, int mode,
+                                    uint64_t rng_seed, uint64_t rng_counter, int64_t *actions, float *logp, float *value,
+                                    float *obs_store, void *scratch, const uint64_t *clock, void *stream,
+                                    uint32_t valid_mask)
+{
+    // n_actions outside [1, 32] is the dims check's to name; the shift is undefined at 32 actions
+    GS_REQUIRE(dims.n_actions <= 0 || dims.n_actions >= 32 || (valid_mask >> dims.n_actions) == 0u,
+               "gs_policy_act_masked: valid_mask 0x%x has bits past n_actions %d", valid_mask, dims.n_actions);
+    return policy_act("gs_policy_act_masked", params, dims, obs, N, mode, rng_seed, rng_counter, actions, logp, value,
+                      obs_store, scratch, clock, stream, valid_mask);
 }
 
 extern "C" int gs_rollout_synth_supported(gs_mlp_dims dims, int *supported)

@@ -26,6 +26,9 @@
 // (template parameter TWO): the heads read h1.
 // No float atomics and no ticket: every sum has a fixed order (rows in a tile, tiles in a workgroup,
 // workgroups by index, parts by index); the per-neuron dead counts are integers.
+// Under an action mask (gs_ppo_rows_update_masked / gs_ppo_rows_loss_masked) the row kernel is the
+// same but for its loss row, loss_row_masked: every head column is formed, the invalid actions'
+// dz is an exact 0, and so are their rows of the head gradient (no column compaction).
 // Compiled with the default -ffp-contract (FMA), as gs_pg.hip: nothing here has to round as the
 // chain's -ffp-contract=off files do, the MFMA products are fmaf chains anyway, and the contracted
 // vector-ALU dot products carry one rounding less per term.
@@ -93,6 +96,8 @@ struct RowsArgs {
     const int32_t *stop;        // null unless target_kl is set
     int T, N, B, ntiles, stride, nparts, act_stats;
     LossArgs la;
+    uint32_t valid;             // the masked head's valid actions (k_ppo_rows<.., true> only): behind every
+                                // field the unmasked kernel reads, whose argument offsets so stay as they were
 };
 
 struct RowsStepArgs {
@@ -163,7 +168,9 @@ __device__ __forceinline__ void rows_layer1(const float *__restrict__ W, const f
     }
 }
 
-template <int AMAX, bool TWO>
+// MASKED: the rows' loss is loss_row_masked over a.valid (gs_head.h), on the logits in LDS; everything
+// else is the same code, so an invalid action's logit is formed and never read, and its dz is an exact 0
+template <int AMAX, bool TWO, bool MASKED>
 __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
 {
     extern __shared__ __align__(16) double lds_d[];
@@ -293,10 +300,15 @@ __global__ void __launch_bounds__(256) k_ppo_rows(RowsLayout L, RowsArgs a)
         if (tid < R) {
             float *dzr = dz + tid * A1;
             if (frow[tid] >= 0) {
-                float zr[AMAX + 1];
+                if constexpr (MASKED) {      // the row's logits where they lie: the valid ones are read, no others
+                    loss_row_masked(z + tid * A1, A, a.valid, fact[tid], folp[tid], fov[tid], fadv[tid], fret[tid], la,
+                                    la.inv_batch, dzr, acc);
+                } else {
+                    float zr[AMAX + 1];
 #pragma unroll
-                for (int c = 0; c < AMAX + 1; ++c) zr[c] = c < A1 ? z[tid * A1 + c] : 0.0f;
-                loss_row<AMAX>(zr, A, fact[tid], folp[tid], fov[tid], fadv[tid], fret[tid], la, la.inv_batch, dzr, acc);
+                    for (int c = 0; c < AMAX + 1; ++c) zr[c] = c < A1 ? z[tid * A1 + c] : 0.0f;
+                    loss_row<AMAX>(zr, A, fact[tid], folp[tid], fov[tid], fadv[tid], fret[tid], la, la.inv_batch, dzr, acc);
+                }
             } else {
                 for (int c = 0; c < A1; ++c) dzr[c] = 0.0f;    // a ragged tile's rows past the minibatch
             }
@@ -602,12 +614,17 @@ int rows_dispatch(const RowsLayout &L, F &&f)
     return with_amax(L.A, [&](auto amax) { return L.two ? f(amax, std::true_type{}) : f(amax, std::false_type{}); });
 }
 
+// valid_mask: 0 = the unmasked head (k_ppo_rows<.., false>, the code of gs_ppo_rows_update / _loss)
 int rows_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_mlp_dims &dims, const gs_ppo_hparams &hp,
              const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n, int64_t adam_step0, float *metrics,
-             int32_t *stop_flag, void *workspace, size_t workspace_bytes, bool do_step, hipStream_t s, const char *what)
+             int32_t *stop_flag, void *workspace, size_t workspace_bytes, bool do_step, hipStream_t s, const char *what,
+             uint32_t valid_mask = 0u)
 {
     int rc = rows_check_dims(dims, what);
     if (rc) return rc;
+    // the shift is undefined at 32 actions, where every bit names an action
+    GS_REQUIRE(dims.n_actions == 32 || (valid_mask >> dims.n_actions) == 0u, "%s: valid_mask 0x%x has bits past "
+               "n_actions %d", what, valid_mask, dims.n_actions);
     GS_REQUIRE(!(hp.flags & GS_HP_BF16), "%s: precision bf16 is a mode of the fused chain; the row-parallel update is "
                                          "fp32 only", what);
     if ((rc = rows_check_batch(batch, ro.T, ro.N, what))) return rc;
@@ -650,14 +667,19 @@ int rows_run(float *params, float *grads, float *adam_m, float *adam_v, const gs
         ra.T = (int)ro.T, ra.N = (int)ro.N, ra.B = (int)batch, ra.ntiles = ws.ntiles, ra.stride = ws.stride;
         ra.nparts = ws.nparts, ra.act_stats = act_stats;
         ra.la = la;
+        ra.valid = valid_mask;
         rc = rows_dispatch(L, [&](auto amax, auto two) {
             constexpr int AMAX = decltype(amax)::value;
             constexpr bool TWO = decltype(two)::value;
-            const int rl = set_lds_limit((const void *)k_ppo_rows<AMAX, TWO>, lds);
-            if (rl) return rl;
-            hipLaunchKernelGGL((k_ppo_rows<AMAX, TWO>), dim3((unsigned)ws.groups), dim3(256), lds, s, L, ra);
-            GS_LAUNCH_CHECK("k_ppo_rows");
-            return (int)GS_OK;
+            auto launch = [&](auto masked) {
+                constexpr bool MASKED = decltype(masked)::value;
+                const int rl = set_lds_limit((const void *)k_ppo_rows<AMAX, TWO, MASKED>, lds);
+                if (rl) return rl;
+                hipLaunchKernelGGL((k_ppo_rows<AMAX, TWO, MASKED>), dim3((unsigned)ws.groups), dim3(256), lds, s, L, ra);
+                GS_LAUNCH_CHECK("k_ppo_rows");
+                return (int)GS_OK;
+            };
+            return valid_mask != 0u ? launch(std::true_type{}) : launch(std::false_type{});
         });
         if (rc) return rc;
         RowsStepArgs sa{};
@@ -708,4 +730,27 @@ extern "C" int gs_ppo_rows_loss(const float *params, float *grads, gs_mlp_dims d
     using namespace gs;
     return rows_run(const_cast<float *>(params), grads, nullptr, nullptr, dims, hp, ro, idx, batch, 1, 0, metrics, nullptr,
                     workspace, workspace_bytes, false, (hipStream_t)stream, "gs_ppo_rows_loss");
+}
+
+// The masked twins (include/gsamd.h): valid_mask bit a set = action a valid, 0 = no mask (the entries above)
+extern "C" int gs_ppo_rows_update_masked(float *params, float *grads, float *adam_m, float *adam_v, gs_mlp_dims dims,
+                                         gs_ppo_hparams hp, gs_rollout_view ro, const int32_t *idx, int64_t batch,
+                                         int64_t n_minibatches, int64_t adam_step0, float *metrics, int32_t *stop_flag,
+                                         void *workspace, size_t workspace_bytes, struct gs_comm *comm, void *stream,
+                                         uint32_t valid_mask)
+{
+    using namespace gs;
+    GS_REQUIRE(comm == nullptr, "gs_ppo_rows_update_masked: the row-parallel update has no gradient exchange, a "
+                                "communicator is not supported (one GPU)");
+    return rows_run(params, grads, adam_m, adam_v, dims, hp, ro, idx, batch, n_minibatches, adam_step0, metrics, stop_flag,
+                    workspace, workspace_bytes, true, (hipStream_t)stream, "gs_ppo_rows_update_masked", valid_mask);
+}
+
+extern "C" int gs_ppo_rows_loss_masked(const float *params, float *grads, gs_mlp_dims dims, gs_ppo_hparams hp,
+                                       gs_rollout_view ro, const int32_t *idx, int64_t batch, float *metrics,
+                                       void *workspace, size_t workspace_bytes, void *stream, uint32_t valid_mask)
+{
+    using namespace gs;
+    return rows_run(const_cast<float *>(params), grads, nullptr, nullptr, dims, hp, ro, idx, batch, 1, 0, metrics, nullptr,
+                    workspace, workspace_bytes, false, (hipStream_t)stream, "gs_ppo_rows_loss_masked", valid_mask);
 }

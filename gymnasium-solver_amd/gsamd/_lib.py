@@ -145,6 +145,13 @@ def _load():
         "gs_ppo_rows_update": (ctypes.c_int, [vp, vp, vp, vp, MlpDims, PPOHparams, RolloutView, vp, i64, i64, i64, vp,
                                               vp, vp, sz, vp, vp]),
         "gs_ppo_rows_loss": (ctypes.c_int, [vp, vp, MlpDims, PPOHparams, RolloutView, vp, i64, vp, vp, sz, vp]),
+        # the masked head's entries: their unmasked sibling's list + valid_mask (bit a set = action a valid)
+        "gs_ppo_rows_update_masked": (ctypes.c_int, [vp, vp, vp, vp, MlpDims, PPOHparams, RolloutView, vp, i64, i64, i64,
+                                                     vp, vp, vp, sz, vp, vp, ctypes.c_uint32]),
+        "gs_ppo_rows_loss_masked": (ctypes.c_int, [vp, vp, MlpDims, PPOHparams, RolloutView, vp, i64, vp, vp, sz, vp,
+                                                   ctypes.c_uint32]),
+        "gs_policy_act_masked": (ctypes.c_int, [vp, MlpDims, vp, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, vp, vp,
+                                                ctypes.c_uint32]),
         "gs_mlp_param_count": (i64, [MlpDims]),
         "gs_policy_scratch_bytes": (sz, [MlpDims, i64]),
         "gs_policy_act": (ctypes.c_int, [vp, MlpDims, vp, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
@@ -268,6 +275,7 @@ EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_norma
             "gs_ppo_update_global", "gs_ppo_update_workspace_bytes",
             "gs_ppo_graph_cache_info", "gs_ppo_exchange_inside_bwd",
             "gs_ppo_rows_workspace_bytes", "gs_ppo_rows_update", "gs_ppo_rows_loss",
+            "gs_ppo_rows_update_masked", "gs_ppo_rows_loss_masked", "gs_policy_act_masked",
             "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
             "gs_cnn_ppo_update_global",
             "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",

@@ -12,13 +12,14 @@ bit-identical initial weights.
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 import torch.nn as nn
 
 from . import _lib
 from ._lib import MlpDims, check, lib, ptr, stream_handle
+from .cnn import valid_mask      # the NatureCNN policy's validation of the same list
 
 
 def param_shapes(obs_dim: int, hidden: Sequence[int], n_actions: int):
@@ -66,10 +67,12 @@ def reference_init(obs_dim: int, hidden: Sequence[int], n_actions: int) -> "Orde
 
 class DeviceMLPActorCritic:
     """ReLU actor-critic with one or two hidden layers whose forward runs in libgsamd kernels
-    (one layer, the reference's mlp_tiny: MlpDims.hidden2 == 0, csrc/gs_mlp1.hip)."""
+    (one layer, the reference's mlp_tiny: MlpDims.hidden2 == 0, csrc/gs_mlp1.hip).  valid_actions
+    (spec.action_space.valid, utils/models.py:285-346): the policy acts and is updated under a
+    MaskedCategorical over those actions (gs_policy_act_masked, gs_ppo_rows_*_masked)."""
 
     def __init__(self, obs_dim: int, hidden_dims: Tuple[int, ...], n_actions: int, device="cuda",
-                 init: bool = True):
+                 init: bool = True, valid_actions: Optional[Sequence[int]] = None):
         if len(hidden_dims) not in (1, 2):
             raise ValueError(f"device MLP path implements one or two hidden layers, got {hidden_dims}")
         self.obs_dim, self.hidden_dims, self.n_actions = int(obs_dim), tuple(int(h) for h in hidden_dims), int(n_actions)
@@ -77,6 +80,8 @@ class DeviceMLPActorCritic:
             raise ValueError(f"hidden layer widths must be positive, got {hidden_dims}")
         self.dims = MlpDims(self.obs_dim, self.hidden_dims[0], self.hidden_dims[1] if len(self.hidden_dims) == 2 else 0,
                             self.n_actions)
+        self.valid_actions = None if valid_actions is None else [int(a) for a in valid_actions]
+        self.valid_mask = valid_mask(self.valid_actions, self.n_actions)      # 0: no mask
         self.n_params = int(lib.gs_mlp_param_count(self.dims))
         if self.n_params != sum(int(torch.Size(s).numel()) for _, s in self.shapes()):
             raise ValueError(f"libgsamd counts {self.n_params} parameters for {self.hidden_dims}")
@@ -135,9 +140,12 @@ class DeviceMLPActorCritic:
             logp = torch.empty(n, dtype=torch.float32, device=self.device)
         if values is None:
             values = torch.empty(n, dtype=torch.float32, device=self.device)
-        check(lib.gs_policy_act(ptr(self.params), self.dims, ptr(obs), n, int(mode), int(rng_seed),
-                                int(rng_counter), ptr(actions), ptr(logp), ptr(values), ptr(obs_store),
-                                ptr(self.scratch(n)), ptr(clock), stream_handle()), "gs_policy_act")
+        args = (ptr(self.params), self.dims, ptr(obs), n, int(mode), int(rng_seed), int(rng_counter), ptr(actions),
+                ptr(logp), ptr(values), ptr(obs_store), ptr(self.scratch(n)), ptr(clock), stream_handle())
+        if self.valid_mask:
+            check(lib.gs_policy_act_masked(*args, self.valid_mask), "gs_policy_act_masked")
+        else:
+            check(lib.gs_policy_act(*args), "gs_policy_act")
         return actions, logp, values
 
     def predict_values(self, obs: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:

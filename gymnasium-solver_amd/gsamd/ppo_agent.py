@@ -107,19 +107,41 @@ class DevicePPOAgent:
             raise ValueError(f"model_id {c.model_id!r} has one hidden layer: its update is fp32 only, "
                              "precision 'bf16' is a mode of the two-hidden-layer chain")
 
+    @property
+    def _mlp_mask(self) -> int:
+        """The MLP policy's action mask (spec.action_space.valid; 0: none).  Before build_models
+        it comes from the config, whose indices the policy then validates."""
+        if self.is_pixel:
+            return 0
+        pm = getattr(self, "policy_model", None)
+        if pm is not None:
+            return int(pm.valid_mask)
+        return 1 if self.config.valid_actions is not None else 0
+
     def _use_rows(self, B: int) -> bool:
         """Minibatches beyond the chain's 1024 rows take the row-parallel update
         (csrc/gs_ppo_rows.hip: gs_ppo_rows_update / gs_ppo_rows_loss); at 1024 rows and below
-        nothing changes."""
-        return not self.is_pixel and int(B) > ROWS_UPDATE_ABOVE
+        nothing changes — but for a masked MLP policy, whose update is that path's masked entries
+        (gs_ppo_rows_update_masked / gs_ppo_rows_loss_masked) at every batch size."""
+        return not self.is_pixel and (int(B) > ROWS_UPDATE_ABOVE or self._mlp_mask != 0)
+
+    def _rows_update(self, *args):
+        """gs_ppo_rows_update, or its masked twin for a masked policy (the same arguments)."""
+        if self._mlp_mask:
+            check(lib.gs_ppo_rows_update_masked(*args, self._mlp_mask), "gs_ppo_rows_update_masked")
+        else:
+            check(lib.gs_ppo_rows_update(*args), "gs_ppo_rows_update")
 
     def _check_rows_update(self) -> None:
-        """batch_size > 1024 on an MLP policy runs the row-parallel update: fp32, one GPU, local
-        minibatches.  What it does not serve is refused here, before any device work."""
+        """batch_size > 1024 on an MLP policy, or a masked one at any batch size, runs the
+        row-parallel update: fp32, one GPU, local minibatches.  What it does not serve is refused
+        here, before any device work."""
         c = self.config
         if not self._use_rows(c.batch_size):
             return
         what = f"batch_size {int(c.batch_size)} > {ROWS_UPDATE_ABOVE} runs the row-parallel PPO update"
+        if int(c.batch_size) <= ROWS_UPDATE_ABOVE:
+            what = f"action_space.valid {list(c.valid_actions)} (a masked MLP policy) runs the row-parallel PPO update"
         if self.world_size > 1:
             raise ValueError(f"{what}: it has no gradient exchange, world_size={self.world_size} is not supported "
                              "(use one GPU)")
@@ -239,7 +261,8 @@ class DevicePPOAgent:
         else:
             if len(shape) != 1:
                 raise ValueError(f"the MLP policy needs flat observations, the env gives {shape}")
-            self.policy_model = DeviceMLPActorCritic(int(shape[0]), c.hidden_dims, n_act, device=self.device)
+            self.policy_model = DeviceMLPActorCritic(int(shape[0]), c.hidden_dims, n_act, device=self.device,
+                                                     valid_actions=c.valid_actions)
 
     def build_rollout_collector(self, stage: str):
         c = self.config
@@ -531,9 +554,12 @@ class DevicePPOAgent:
         elif self._use_rows(B):
             if getattr(self, "_loss_grads", None) is None:      # the entry also leaves the unclipped gradient
                 self._loss_grads = torch.empty_like(self.grads)
-            check(lib.gs_ppo_rows_loss(ptr(self.policy_model.params), ptr(self._loss_grads), self.policy_model.dims,
-                                       self.hparams(), view, ptr(idx), B, ptr(self._step_metrics), ptr(ws), ws.numel(),
-                                       stream_handle()), "gs_ppo_rows_loss")
+            args = (ptr(self.policy_model.params), ptr(self._loss_grads), self.policy_model.dims, self.hparams(), view,
+                    ptr(idx), B, ptr(self._step_metrics), ptr(ws), ws.numel(), stream_handle())
+            if self._mlp_mask:
+                check(lib.gs_ppo_rows_loss_masked(*args, self._mlp_mask), "gs_ppo_rows_loss_masked")
+            else:
+                check(lib.gs_ppo_rows_loss(*args), "gs_ppo_rows_loss")
         else:
             check(lib.gs_ppo_loss(ptr(self.policy_model.params), self.policy_model.dims, self.hparams(), view,
                                   ptr(idx), B, ptr(self._step_metrics), ptr(ws), stream_handle()), "gs_ppo_loss")
@@ -568,10 +594,9 @@ class DevicePPOAgent:
                                         ptr(self.stop_flag), ptr(ws), self.comm, stream_handle()),
                   "gs_cnn_ppo_update")
         elif self._use_rows(B):
-            check(lib.gs_ppo_rows_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
-                                         ptr(self.adam_v), self.policy_model.dims, self.hparams(), view, ptr(idx), B, 1,
-                                         self.adam_step - 1, ptr(rec), ptr(self.stop_flag), ptr(ws), ws.numel(),
-                                         self.comm, stream_handle()), "gs_ppo_rows_update")
+            self._rows_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
+                              self.policy_model.dims, self.hparams(), view, ptr(idx), B, 1, self.adam_step - 1, ptr(rec),
+                              ptr(self.stop_flag), ptr(ws), ws.numel(), self.comm, stream_handle())
         else:
             check(lib.gs_ppo_minibatch_step(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
                                             ptr(self.adam_v), self.policy_model.dims, self.hparams(), view,
@@ -645,11 +670,10 @@ class DevicePPOAgent:
                                         ptr(self.stop_flag), ptr(self.workspace), self.comm, stream_handle()),
                   "gs_cnn_ppo_update")
         elif self._use_rows(self.batch_size):
-            check(lib.gs_ppo_rows_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
-                                         ptr(self.adam_v), self.policy_model.dims, self.hparams(), buf.view(), ptr(idx),
-                                         self.batch_size, self.n_minibatches, self.adam_step, ptr(self.metrics_buf),
-                                         ptr(self.stop_flag), ptr(self.workspace), self.workspace.numel(), self.comm,
-                                         stream_handle()), "gs_ppo_rows_update")
+            self._rows_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m), ptr(self.adam_v),
+                              self.policy_model.dims, self.hparams(), buf.view(), ptr(idx), self.batch_size,
+                              self.n_minibatches, self.adam_step, ptr(self.metrics_buf), ptr(self.stop_flag),
+                              ptr(self.workspace), self.workspace.numel(), self.comm, stream_handle())
         else:
             check(lib.gs_ppo_update(ptr(self.policy_model.params), ptr(self.grads), ptr(self.adam_m),
                                     ptr(self.adam_v), self.policy_model.dims, self.hparams(), buf.view(), ptr(idx),

@@ -7,7 +7,8 @@ config_mountaincar.json for the three MountainCar-v0 variants are the machine-ge
 the tests compare against).  The reference leaves MountainCar-v0's n_envs at "auto", the host's core
 count (utils/config.py:482-485): the record keeps "auto" and the presets take 32; the same holds for
 FrozenLake-v1's ppo / ppo_deterministic and Taxi-v3's ppo (config_toytext.json) and for Bandit-v0's ppo
-(config_cartpole_bandit.json, which also records CartPole-v1:ppo_rewardshaped).  MODEL_REGISTRY
+(config_cartpole_bandit.json, which also records CartPole-v1:ppo_rewardshaped); config_pong_objects.json
+records ALE-Pong-v5's objects_ppo / objects_deterministic_ppo (masked MLP policies).  MODEL_REGISTRY
 mirrors utils/model_registry.py:17-76.
 """
 
@@ -130,6 +131,31 @@ PRESETS = {
         n_epochs=15, gamma=0.99, gae_lambda=0.95, clip_range=0.2, ent_coef=0.01, policy_lr=0.0003,
         model_id="cnn_nature", max_env_steps=5000000.0, obs_type="rgb", frame_stack=4,
         spec={"action_space": {"discrete": 18, "valid": [0, 3, 4]}}),
+    # Pong on extracted objects (config/environments/ALE-Pong-v5.yaml:180-242; record:
+    # tests/golden/config_pong_objects.json): 12 features from the host's PongV5_FeatureExtractor, the full
+    # 18-action space masked down to NOOP / RIGHT / LEFT.  No device dynamics: env= / env_factory= as the
+    # rgb configs.  batch_size 2048 and the mask both put these on the row-parallel update's masked entries.
+    "ALE-Pong-v5:objects_ppo": dict(
+        _COMMON, env_id="ALE/Pong-v5", project_id="ALE-Pong-v5_objects", n_envs=32, n_steps=1024, batch_size=2048,
+        n_epochs=8, gamma=0.995, gae_lambda=0.96, clip_range=0.3, ent_coef=0.04, policy_lr=0.0055,
+        model_id="mlp_small", max_env_steps=3500000, obs_type="objects", accelerator="cpu",
+        env_wrappers=[{"id": "PongV5_FeatureExtractor", "action_ids": [0, 3, 4]}],
+        schedules={"policy_lr": {"schedule": "linear", "start_value": 0.0055, "end_value": 0.00015, "start": 0.0,
+                                 "end": 0.92, "warmup": 0.0},
+                   "clip_range": {"schedule": "linear", "start_value": 0.3, "end_value": 0.08, "start": 0.5,
+                                  "end": 0.85, "warmup": 0.0},
+                   "ent_coef": {"schedule": "linear", "start_value": 0.04, "end_value": 0.0001, "start": 0.48,
+                                "end": 0.65, "warmup": 0.0}},
+        spec={"action_space": {"discrete": 18, "valid": [0, 3, 4]},
+              "observation_space": {"default": "state", "variants": {"state": {"shape": [12], "dtype": "float32"}}}}),
+    "ALE-Pong-v5:objects_deterministic_ppo": dict(
+        _COMMON, env_id="ALE/Pong-v5", project_id="ALE-Pong-v5_objects_deterministic", n_envs=32, n_steps=1024,
+        batch_size=2048, n_epochs=10, gamma=0.99, gae_lambda=0.95, clip_range=0.1, ent_coef=0.0, policy_lr=0.01,
+        model_id="mlp_tiny", max_env_steps=1500000, obs_type="objects", accelerator="cpu",
+        env_kwargs={"repeat_action_probability": 0.0},
+        env_wrappers=[{"id": "PongV5_FeatureExtractor", "action_ids": [0, 3, 4]}],
+        spec={"action_space": {"discrete": 18, "valid": [0, 3, 4]},
+              "observation_space": {"default": "state", "variants": {"state": {"shape": [12], "dtype": "float32"}}}}),
     "ALE-Breakout-v5:rgb_ppo": dict(
         _COMMON, env_id="ALE/Breakout-v5", project_id="ALE-Breakout-v5_rgb", n_envs=32, n_steps=128,
         batch_size=1024, n_epochs=4, gamma=0.99, gae_lambda=0.95, clip_range=0.1, ent_coef=0.01,

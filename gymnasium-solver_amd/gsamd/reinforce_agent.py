@@ -57,6 +57,9 @@ class DeviceREINFORCEAgent(DevicePPOAgent):
         if len(tuple(c.hidden_dims)) != 2:
             raise ValueError(f"model_id {c.model_id!r}: the REINFORCE update serves two hidden layers, a policy with "
                              "one hidden layer is not supported")
+        if c.valid_actions is not None:
+            raise ValueError(f"action_space.valid {list(c.valid_actions)}: the REINFORCE update has no masked head "
+                             "(the masked MLP policy trains with algo_id 'ppo')")
         if int(world_size) > 1 or comm:
             raise ValueError(f"the REINFORCE update has no gradient exchange: world_size={world_size} is not "
                              "supported (use one GPU)")

@@ -701,6 +701,8 @@ class DeviceRolloutCollector:
 
     @staticmethod
     def _one_launch_supported(env, pm) -> bool:
+        if getattr(pm, "valid_mask", 0):     # the one-launch rollouts have no masked head: step loop / step graph
+            return False
         v = ctypes.c_int()
         if isinstance(env, DeviceSyntheticVecEnv):
             check(lib.gs_rollout_synth_supported(pm.dims, ctypes.byref(v)), "gs_rollout_synth_supported")
@@ -717,8 +719,8 @@ class DeviceRolloutCollector:
     @staticmethod
     def _one_launch_mlp1_supported(env, pm) -> bool:
         """A one-hidden-layer policy on a device env that has a rollout1_into, when
-        gs_rollout1_supported takes the shape."""
-        if int(getattr(pm.dims, "hidden2", -1)) != 0 or not getattr(env, "device_native", False) or \
+        gs_rollout1_supported takes the shape; never for a masked policy (no masked head there)."""
+        if getattr(pm, "valid_mask", 0) or int(getattr(pm.dims, "hidden2", -1)) != 0 or not getattr(env, "device_native", False) or \
                 not hasattr(env, "rollout1_into"):
             return False
         v = ctypes.c_int()

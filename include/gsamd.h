@@ -141,6 +141,20 @@ int gs_policy_act(const float *params_dev, gs_mlp_dims dims, const float *obs_de
                   uint64_t rng_seed, uint64_t rng_counter, int64_t *actions_dev, float *logp_dev,
                   float *value_dev, float *obs_store_dev, void *scratch_dev, const uint64_t *clock_dev,
                   void *stream);
+/* gs_policy_act under an action mask: the policy the reference builds with
+ * valid_actions = spec.action_space.valid (utils/models.py:285-346, MaskedCategorical,
+ * utils/distributions.py:8-82).  valid_mask: bit a set = action a valid.  The softmax runs over the
+ * valid actions only (logp = z[action] - logsumexp over them); mode 1 takes the first maximum among
+ * them; mode 0 draws from them with gs_policy_act's uniform under the same key, the inverse CDF in
+ * index order, the fallback the last valid action; mode 2 replays (a recorded action outside the
+ * valid set is the caller's error: its logp is unspecified, nothing is read out of range).  The
+ * envelope, the scratch and the graph capture are gs_policy_act's; valid_mask == 0 means no mask and
+ * gives gs_policy_act's bytes; bits at or beyond n_actions are GS_E_INVALID.  The value needs no
+ * mask: gs_policy_value serves a masked policy as it is. */
+int gs_policy_act_masked(const float *params_dev, gs_mlp_dims dims, const float *obs_dev, int64_t N, int mode,
+                         uint64_t rng_seed, uint64_t rng_counter, int64_t *actions_dev, float *logp_dev,
+                         float *value_dev, float *obs_store_dev, void *scratch_dev, const uint64_t *clock_dev,
+                         void *stream, uint32_t valid_mask);
 
 /* A whole rollout of the synthetic env (gs_env_*) in ONE launch, for MLP policies whose weights
  * fit in LDS (gs_rollout_synth_supported; the C3 shapes do, C2's 256x256 W2 does not): per
@@ -513,6 +527,23 @@ int gs_ppo_rows_update(float *params_dev, float *grads_dev, float *adam_m_dev, f
 int gs_ppo_rows_loss(const float *params_dev, float *grads_dev, gs_mlp_dims dims, gs_ppo_hparams hp,
                      gs_rollout_view rollout, const int32_t *idx_dev, int64_t batch, float *metrics_dev,
                      void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The two entries above under an action mask (valid_mask: bit a set = action a valid), for a policy
+ * that acts through gs_policy_act_masked: the envelope, workspace, record, KL stop, GS_HP_ACT_STATS
+ * and determinism contract are unchanged.  Per row the normalisation runs over the valid actions,
+ * the entropy is MaskedCategorical's -sum_valid p logf(p + 1e-8f), and dLoss/dlogit of an invalid
+ * action is an exact 0: the invalid rows of policy_head.weight / .bias get a zero gradient, their
+ * Adam moments stay 0 and their parameters keep their bytes.  The row kernel forms every head column
+ * and zeroes the invalid ones' gradient (no column compaction).  valid_mask == 0 means no mask and
+ * gives the unmasked entries' bytes; bits at or beyond n_actions are GS_E_INVALID; a recorded action
+ * outside the valid set is the caller's error (values unspecified, no out-of-range access). */
+int gs_ppo_rows_update_masked(float *params_dev, float *grads_dev, float *adam_m_dev, float *adam_v_dev,
+                              gs_mlp_dims dims, gs_ppo_hparams hp, gs_rollout_view rollout, const int32_t *idx_dev,
+                              int64_t batch, int64_t n_minibatches, int64_t adam_step0, float *metrics_dev,
+                              int32_t *stop_flag_dev, void *workspace_dev, size_t workspace_bytes,
+                              struct gs_comm *comm, void *stream, uint32_t valid_mask);
+int gs_ppo_rows_loss_masked(const float *params_dev, float *grads_dev, gs_mlp_dims dims, gs_ppo_hparams hp,
+                            gs_rollout_view rollout, const int32_t *idx_dev, int64_t batch, float *metrics_dev,
+                            void *workspace_dev, size_t workspace_bytes, void *stream, uint32_t valid_mask);
 
 /* ---------------------------------------------------------------- NatureCNN actor-critic (C4/C5)
  * Replaces CNNActorCritic (utils/models.py:347-455; conv 8x8s4 -> 4x4s2 -> 3x3s1 with 32/64/64
