@@ -127,6 +127,24 @@ def _load():
     L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
     vp, i32, i64, u64, f32, f64, sz = (ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64,
                                        ctypes.c_float, ctypes.c_double, ctypes.c_size_t)
+    # The env and rollout entries' lists, from the groups gsamd.rollout.DeviceVecEnv forms its calls of:
+    # an env's own group (its tensors and parameters), then per entry
+    #   reset:   group, N, seed, env_offset, stream
+    #   step:    group, actions, N, max_steps, seed, env_offset, 3 rows, 3 episode counters, stream
+    #   rollout: head, [env_kind,] group, max_steps, seed, env_offset, 3 episode counters, 7 rows, stream
+    plain = [vp, vp, vp, vp]                                   # state, meta, ep_ret, obs
+    groups = {"cartpole": plain, "acrobot": plain,
+              "cartpole_shaped": [vp, vp, vp, vp, vp, CartPoleWrappers],       # state, prev_phi, meta, ..., wrappers
+              "mountaincar": [vp, vp, vp, vp, vp, MountainCarWrappers],        # ..., obs, counts, wrappers
+              "bandit": [vp, vp, vp, BanditSpec],                              # meta, ep_ret, obs, spec: no state
+              "tabular": [vp, vp, vp, vp, TabularSpec, vp, vp, vp, vp]}        # ..., obs, spec, 3 tables, starts
+    reset_tail = [i64, u64, i64, vp]
+    step_tail = [vp, i64, i32, u64, i64] + [vp] * 7
+    head = [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64]     # params, dims, N, T, mode, rng_seed, counter0
+    run = [i32, u64, i64, vp, vp, vp]                          # max_steps, seed, env_offset, the counters
+    rows = [vp] * 8                                            # the buffer's seven rows, the stream
+    rollouts = {"env": head + [ctypes.c_int] + plain + run + rows,
+                **{x: head + groups[x] + run + rows for x in ("cartpole_shaped", "mountaincar", "bandit", "tabular")}}
     sig = {
         "gs_abi_version": (ctypes.c_int, []),
         "gs_last_error": (ctypes.c_char_p, []),
@@ -157,11 +175,9 @@ def _load():
         "gs_policy_act": (ctypes.c_int, [vp, MlpDims, vp, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp, vp, vp]),
         "gs_policy_value": (ctypes.c_int, [vp, MlpDims, vp, i64, vp, vp, vp]),
         "gs_rollout_synth_supported": (ctypes.c_int, [MlpDims, vp]),
-        "gs_rollout_synth": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, i32, i32, f32,
-                                            u64, i64, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        # state, ep_ret, obs, episode_len, truncate_every, reward, seed, env_offset, step count, the counters
+        "gs_rollout_synth": (ctypes.c_int, head + [vp, vp, vp, i32, i32, f32, u64, i64, u64, vp, vp, vp] + rows),
         "gs_rollout_env_supported": (ctypes.c_int, [MlpDims, ctypes.c_int, vp]),
-        "gs_rollout_env": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, ctypes.c_int, vp, vp, vp, vp,
-                                          i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gs_env_reset": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, u64, i64, vp]),
         "gs_env_step": (ctypes.c_int, [vp, vp, vp, i64, i32, i32, i32, f32, u64, i64, u64, vp, vp, vp, vp, vp,
                                        vp, vp, vp]),
@@ -195,44 +211,15 @@ def _load():
                                        f32, vp, ctypes.c_int, vp]),
         "gs_fc_gemm": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, i64, i64, i64, vp, i64, vp, i64, vp, i64, vp, vp,
                                       vp]),
-        "gs_cartpole_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, u64, i64, vp]),
-        "gs_cartpole_step": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
-        "gs_acrobot_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, u64, i64, vp]),
-        "gs_acrobot_step": (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
-        "gs_mountaincar_reset": (ctypes.c_int, [vp, vp, vp, vp, vp, MountainCarWrappers, i64, u64, i64, vp]),
-        "gs_mountaincar_step": (ctypes.c_int, [vp, vp, vp, vp, vp, MountainCarWrappers, vp, i64, i32, u64, i64, vp, vp,
-                                               vp, vp, vp, vp, vp]),
-        "gs_rollout_mountaincar": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
-                                                  MountainCarWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                  vp, vp, vp]),
-        "gs_cartpole_shaped_reset": (ctypes.c_int, [vp, vp, vp, vp, vp, CartPoleWrappers, i64, u64, i64, vp]),
-        "gs_cartpole_shaped_step": (ctypes.c_int, [vp, vp, vp, vp, vp, CartPoleWrappers, vp, i64, i32, u64, i64, vp, vp,
-                                                   vp, vp, vp, vp, vp]),
-        "gs_rollout_cartpole_shaped": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
-                                                      CartPoleWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp,
-                                                      vp, vp, vp, vp]),
-        "gs_bandit_reset": (ctypes.c_int, [vp, vp, vp, BanditSpec, i64, vp]),
-        "gs_bandit_step": (ctypes.c_int, [vp, vp, vp, BanditSpec, vp, i64, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp]),
-        "gs_rollout_bandit": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, BanditSpec,
-                                             i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "gs_tabular_reset": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, i64, u64, i64, vp]),
-        "gs_tabular_step": (ctypes.c_int, [vp, vp, vp, vp, TabularSpec, vp, vp, vp, vp, vp, i64, i32, u64, i64, vp, vp,
-                                           vp, vp, vp, vp, vp]),
-        # the one-hidden-layer policy's one-launch rollouts: their two-hidden-layer siblings' lists
+        **{f"gs_{x}_reset": (ctypes.c_int, g + reset_tail) for x, g in groups.items() if x not in ("bandit", "tabular")},
+        "gs_bandit_reset": (ctypes.c_int, groups["bandit"] + [i64, vp]),               # no reset draw: no seed, no offset
+        "gs_tabular_reset": (ctypes.c_int, plain + [TabularSpec, vp] + reset_tail),    # spec, starts: none of the tables
+        **{f"gs_{x}_step": (ctypes.c_int, g + step_tail) for x, g in groups.items()},
+        # the one-launch rollouts; a one-hidden-layer policy's entry takes its two-hidden-layer sibling's
+        # list (the same object), and the tabular env has only that one
+        **{f"gs_rollout_{x}": (ctypes.c_int, a) for x, a in rollouts.items() if x != "tabular"},
+        **{f"gs_rollout1_{x}": (ctypes.c_int, a) for x, a in rollouts.items()},
         "gs_rollout1_supported": (ctypes.c_int, [MlpDims, vp]),
-        "gs_rollout1_env": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, ctypes.c_int, vp, vp, vp, vp,
-                                           i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "gs_rollout1_cartpole_shaped": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp,
-                                                       vp, CartPoleWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp,
-                                                       vp, vp, vp, vp, vp]),
-        "gs_rollout1_mountaincar": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp, vp,
-                                                   MountainCarWrappers, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
-                                                   vp, vp, vp]),
-        "gs_rollout1_bandit": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, BanditSpec,
-                                              i32, u64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-        "gs_rollout1_tabular": (ctypes.c_int, [vp, MlpDims, i64, i64, ctypes.c_int, u64, u64, vp, vp, vp, vp,
-                                               TabularSpec, vp, vp, vp, vp, i32, u64, i64, vp, vp, vp, vp, vp, vp, vp,
-                                               vp, vp, vp, vp]),
         "gs_atari_preprocess": (ctypes.c_int, [vp, i64, i32, i32, vp, vp]),
         "gs_atari_render": (ctypes.c_int, [vp, i64, u64, i64, u64, vp]),
         "gs_atari_env_reset": (ctypes.c_int, [vp, vp, vp, vp, i64, i32, i32, i32, i32, u64, i64, vp]),
@@ -261,33 +248,10 @@ def _load():
     if L.gs_abi_version() != GS_ABI_VERSION:
         raise ImportError(f"{LIB_PATH} implements C-ABI version {L.gs_abi_version()}, this binding version "
                           f"{GS_ABI_VERSION}: rebuild the library (__graft_entry__.build())")
-    return L
+    return L, tuple(sig)
 
 
-lib = _load()
-EXPORTED = ("gs_abi_version", "gs_last_error", "gs_build_source_hash", "gs_normalize_advantages_scratch_bytes", "gs_normalize_advantages",
-            "gs_cnn_activation_stats", "gs_gae_f32", "gs_sampler_stream_i32", "gs_mlp_param_count",
-            "gs_mc_returns_f32", "gs_pg_update_workspace_bytes", "gs_pg_update", "gs_pg_loss",
-            "gs_policy_scratch_bytes", "gs_policy_act", "gs_policy_value", "gs_rollout_synth_supported",
-            "gs_rollout_synth", "gs_rollout_env_supported", "gs_rollout_env", "gs_env_reset", "gs_env_step",
-            "gs_episode_stats", "gs_episode_window",
-            "gs_ppo_workspace_bytes", "gs_ppo_minibatch_step", "gs_ppo_loss", "gs_mlp_activation_stats", "gs_ppo_stage", "gs_ppo_update",
-            "gs_ppo_update_global", "gs_ppo_update_workspace_bytes",
-            "gs_ppo_graph_cache_info", "gs_ppo_exchange_inside_bwd",
-            "gs_ppo_rows_workspace_bytes", "gs_ppo_rows_update", "gs_ppo_rows_loss",
-            "gs_ppo_rows_update_masked", "gs_ppo_rows_loss_masked", "gs_policy_act_masked",
-            "gs_cnn_param_count", "gs_cnn_workspace_bytes", "gs_cnn_workspace_hidden_offset", "gs_cnn_workspace_act_offset", "gs_cnn_policy_act", "gs_cnn_ppo_loss", "gs_cnn_ppo_update",
-            "gs_cnn_ppo_update_global",
-            "gs_gemm_f32", "gs_fc_gemm", "gs_cartpole_reset", "gs_cartpole_step", "gs_acrobot_reset", "gs_acrobot_step",
-            "gs_mountaincar_reset", "gs_mountaincar_step", "gs_rollout_mountaincar",
-            "gs_cartpole_shaped_reset", "gs_cartpole_shaped_step", "gs_rollout_cartpole_shaped", "gs_bandit_reset",
-            "gs_bandit_step", "gs_rollout_bandit", "gs_tabular_reset", "gs_tabular_step",
-            "gs_rollout1_supported", "gs_rollout1_env", "gs_rollout1_cartpole_shaped", "gs_rollout1_mountaincar",
-            "gs_rollout1_bandit", "gs_rollout1_tabular", "gs_atari_preprocess", "gs_atari_render", "gs_atari_env_reset", "gs_atari_env_step", "gs_comm_unique_id",
-            "gs_comm_init", "gs_comm_xgmi_create", "gs_comm_xgmi_connect", "gs_comm_status", "gs_comm_error_record",
-            "gs_comm_xgmi_set_colocation", "gs_comm_xgmi_set_bwd_exchange", "gs_comm_xgmi_reset",
-            "gs_comm_allreduce_mean_f32", "gs_comm_allreduce_sum_f64", "gs_ppo_global_adv_stats",
-            "gs_ppo_global_records", "gs_comm_info", "gs_comm_destroy")
+lib, EXPORTED = _load()          # the library and the names of every entry declared above
 
 
 def check(rc: int, what: str = "") -> None:

@@ -26,12 +26,10 @@ import torch
 import ctypes
 
 from ._lib import ACT_SLOT, GS_HP_ACT_STATS, GS_HP_BF16, GS_NUM_METRICS, M, PPOGlobal, PPOHparams, RolloutView, RolloutViewU8, check, lib, ptr, stream_handle
-from .atari_env import DeviceAtariVecEnv
-from .config import TABULAR_KINDS, device_env_kind, resolve_bandit_env, resolve_tabular_env
+from .config import device_env_kind
 from .cnn import DeviceCNNActorCritic
 from .policy import DeviceMLPActorCritic
-from .rollout import (DeviceAcrobotVecEnv, DeviceBanditVecEnv, DeviceCartPoleVecEnv, DeviceMountainCarVecEnv,
-                      DeviceRolloutCollector, DeviceSyntheticVecEnv, DeviceTabularVecEnv)
+from .rollout import BANDIT_MAX_TRAINABLE_ARMS, DeviceRolloutCollector, device_env_from_config  # noqa: F401
 from .samplers import IndexStreamPrefetcher, MultiPassRandomSampler, index_stream, rank_share
 from .distributed import allreduce_sum_f64, broadcast_int, check_replicas, comm_status, world_active
 from . import distributed as _dist
@@ -40,7 +38,6 @@ from .schedules import SCHEDULABLE, build_schedulers
 
 STAGES = ("train",)
 ROWS_UPDATE_ABOVE = 1024            # the chain entries' largest minibatch; beyond it the row-parallel update
-BANDIT_MAX_TRAINABLE_ARMS = 15      # see _device_env: what the MLP update's forward staging covers
 
 
 class MinibatchIndices:
@@ -160,72 +157,10 @@ class DevicePPOAgent:
         if env is None and self.env_factory is not None and device_env_kind(c) is None:
             env = self.env_factory(stage)
         if env is None:
-            env = self._device_env(stage)
+            env = device_env_from_config(c, stage, self.rank, self.device)
         if int(getattr(env, "num_envs", c.n_envs)) != int(c.n_envs):
             raise ValueError(f"env has {env.num_envs} envs, config.n_envs is {c.n_envs}")
         self._envs[stage] = env
-
-    def _device_env(self, stage: str):
-        c = self.config
-        kind = device_env_kind(c)
-        if kind is None:
-            raise ValueError(
-                f"env_id {c.env_id!r} (obs_type {c.obs_type!r}) has no device dynamics: pass env=<the gymnasium "
-                f"VectorEnv build_env_from_config(config, seed=config.seed_train) returns> (or env_factory=), or "
-                f"set env_dynamics='synthetic' for the fixed-length synthetic env of the benchmark")
-        off = self.rank * c.n_envs
-        train = stage == "train"
-        if kind == "cartpole":
-            if self.is_pixel or c.resolved_obs_dim() != 4 or c.resolved_n_actions() != 2:
-                raise ValueError("env_dynamics='cartpole' needs vector observations of dim 4 and 2 actions")
-            # every stage's env carries the config's reward shaper (the reference builds each from the same list)
-            return DeviceCartPoleVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
-                                        max_steps=int(c.max_episode_steps or 500),
-                                        wrappers=list(c.env_wrappers or ()), device=self.device)
-        if kind == "bandit":
-            b = resolve_bandit_env(c)
-            if self.is_pixel or b is None or c.resolved_n_actions() != b["n_arms"]:
-                raise ValueError("env_dynamics='bandit' needs env_id Bandit-v0 with env_kwargs the device applies "
-                                 "(gsamd.config.resolve_bandit_env)")
-            if b["n_arms"] > BANDIT_MAX_TRAINABLE_ARMS:
-                # the env kernels take 32 arms; the two-hidden-layer update does not yet (measured at 20 arms:
-                # NaN / inf losses).  Its forward stages a 16-row tile's observations and the 16 x (A + 1) head
-                # weights with one element per thread of 256: complete only for obs_dim <= 16, n_actions <= 15.
-                raise ValueError(f"Bandit-v0 with n_arms={b['n_arms']}: the MLP update serves obs_dim <= 16 and "
-                                 f"n_actions <= 15, so at most {BANDIT_MAX_TRAINABLE_ARMS} arms train on the device")
-            return DeviceBanditVecEnv(c.n_envs, n_arms=b["n_arms"], means=b["means"], stds=b["stds"],
-                                      episode_length=b["episode_length"],
-                                      seed=c.seed_train if train else c.seed_val, env_offset=off,
-                                      max_steps=int(c.max_episode_steps or 0) or None, device=self.device)
-        if kind == "acrobot":
-            if self.is_pixel or c.resolved_obs_dim() != 6 or c.resolved_n_actions() != 3:
-                raise ValueError("env_dynamics='acrobot' needs vector observations of dim 6 and 3 actions")
-            return DeviceAcrobotVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
-                                       max_steps=int(c.max_episode_steps or 500), device=self.device)
-        if kind == "mountaincar":
-            if self.is_pixel or c.resolved_obs_dim() != 2 or c.resolved_n_actions() != 3:
-                raise ValueError("env_dynamics='mountaincar' needs vector observations of dim 2 and 3 actions")
-            # every stage's env carries the config's wrappers (the reference builds each from the same list)
-            return DeviceMountainCarVecEnv(c.n_envs, seed=c.seed_train if train else c.seed_val, env_offset=off,
-                                           max_steps=int(c.max_episode_steps or 200),
-                                           wrappers=list(c.env_wrappers or ()), device=self.device)
-        if kind in TABULAR_KINDS:
-            tab = resolve_tabular_env(c)
-            if self.is_pixel or tab is None or tab["kind"] != kind:
-                raise ValueError(f"env_dynamics={kind!r} needs env_id FrozenLake-v1 / Taxi-v3 with exactly the "
-                                 "DiscreteEncoder wrapper (gsamd.config.resolve_tabular_env)")
-            return DeviceTabularVecEnv(c.n_envs, kind=kind, encoding=tab["encoding"], map_name=tab["map_name"],
-                                       is_slippery=tab["is_slippery"], seed=c.seed_train if train else c.seed_val,
-                                       env_offset=off, max_steps=int(c.max_episode_steps or 0) or None,
-                                       device=self.device)
-        seed = c.seed if train else c.seed + 1000
-        if self.is_pixel:
-            return DeviceAtariVecEnv(n_envs=c.n_envs, n_actions=c.resolved_n_actions(), episode_len=c.episode_len,
-                                     seed=seed, truncate_every=c.truncate_every, env_offset=off,
-                                     frame_stack=int(c.frame_stack or 4), device=self.device)
-        return DeviceSyntheticVecEnv(n_envs=c.n_envs, obs_dim=c.resolved_obs_dim(), n_actions=c.resolved_n_actions(),
-                                     episode_len=c.episode_len, seed=seed, truncate_every=c.truncate_every,
-                                     env_offset=off, device=self.device)
 
     def get_env(self, stage: str):
         return self._envs[stage]

@@ -33,18 +33,35 @@ import torch
 from ._lib import (GS_BANDIT_MAX_ARMS, GS_ENCODINGS, GS_ENV_ACROBOT, GS_ENV_BANDIT, GS_ENV_CARTPOLE,
                    GS_ENV_MOUNTAINCAR, GS_MC_BONUS_TYPES, GS_MC_WRAP_BONUS, GS_MC_WRAP_NONE, GS_MC_WRAP_SHAPER,
                    BanditSpec, CartPoleWrappers, MountainCarWrappers, TabularSpec, check, lib, ptr, stream_handle)
-from .config import bandit_arms, resolve_cartpole_wrappers, resolve_mountaincar_wrappers
+from .atari_env import DeviceAtariVecEnv
+from .config import (TABULAR_KINDS, bandit_arms, device_env_kind, resolve_bandit_env, resolve_cartpole_wrappers,
+                     resolve_mountaincar_wrappers, resolve_tabular_env)
 from .distributed import allreduce_sum_f64
 from .rollout_stats import RollingWindow
+
+BANDIT_MAX_TRAINABLE_ARMS = 15      # see DeviceBanditVecEnv.from_config: what the MLP update's forward staging covers
+
+
+def _is_pixel(c) -> bool:
+    return str(getattr(c, "obs_type", "vector")) == "rgb"
 
 
 class DeviceVecEnv:
     """What the device env classes share: the tensors every env kernel takes (meta, the running
-    return, the observation, the three finished-episode counters) and the argument groups of the
-    one-launch rollout entries.  An env class adds its own tensors and parameters, reset(),
-    step_into() and, where its kernels have one, rollout_into(): its one-launch rollout call."""
+    return, the observation, the three finished-episode counters) and the four calls into the
+    library: reset(), step_into(), rollout_into() and rollout1_into().  An env class adds its own
+    tensors and parameters, names its entries, and states once, in _env_args(), the argument group
+    every one of them takes (include/gsamd.h: `state, meta, ep_ret, obs, ...`); each call's list is
+    formed here from that group.  An entry is looked up on this module's `lib` when it is called."""
 
     device_native = True
+    entry_stem = None            # "<x>": reset() calls gs_<x>_reset, step_into() gs_<x>_step
+    rollout_entry = None         # the gs_rollout_* entry (two hidden layers) behind rollout_into(), or None
+    rollout1_entry = None        # the gs_rollout1_* entry (one hidden layer) behind rollout1_into(), or None
+    env_kind = None              # GS_ENV_*: what gs_rollout_env / gs_rollout1_env and gs_rollout_env_supported take
+    # One-launch rollouts (two hidden layers) are the default only up to this many envs.  None = always.
+    one_launch_max_envs = None
+    needs_actions = "the env needs the step's actions"       # step_into()'s refusal without them
 
     def _alloc(self, n_envs, obs_dim, n_actions, seed, env_offset, device, meta=True):
         self.num_envs, self.obs_dim, self.n_actions = int(n_envs), int(obs_dim), int(n_actions)
@@ -74,9 +91,68 @@ class DeviceVecEnv:
         return (ptr(buf.obs), ptr(buf.actions), ptr(buf.logprobs), ptr(buf.values), ptr(buf.rewards),
                 ptr(buf.dones), ptr(buf.timeouts), stream_handle())
 
+    def _env_args(self):
+        """The env's own tensors and parameters, in the order every one of its entries takes them."""
+        raise NotImplementedError
+
+    def _reset_args(self):
+        """What gs_<x>_reset takes before the stream."""
+        return (*self._env_args(), self.num_envs, self.seed, self.env_offset)
+
+    def reset(self):
+        entry = f"gs_{self.entry_stem}_reset"
+        check(getattr(lib, entry)(*self._reset_args(), stream_handle()), entry)
+        return self.obs, {}
+
+    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
+        """One vector step into the rollout rows (clock / step are the synthetic env's)."""
+        if actions is None:
+            raise ValueError(self.needs_actions)
+        entry = f"gs_{self.entry_stem}_step"
+        check(getattr(lib, entry)(*self._env_args(), ptr(actions), self.num_envs, self.max_steps, self.seed,
+                                  self.env_offset, ptr(rewards_row), ptr(dones_row), ptr(timeouts_row),
+                                  *self._episode_counters(), stream_handle()), entry)
+
+    def _rollout(self, entry, pm, buf, mode, rng_seed, counter0):
+        if entry is None:
+            raise NotImplementedError(f"{type(self).__name__} has no one-launch rollout of this form")
+        kind = (int(self.env_kind),) if entry in ("gs_rollout_env", "gs_rollout1_env") else ()
+        check(getattr(lib, entry)(*self._policy_args(pm, buf, mode, rng_seed, counter0), *kind, *self._env_args(),
+                                  self.max_steps, self.seed, self.env_offset, *self._episode_counters(),
+                                  *self._row_args(buf)), entry)
+
+    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
+        """The whole rollout of a two-hidden-layer policy in one launch."""
+        self._rollout(self.rollout_entry, pm, buf, mode, rng_seed, counter0)
+
+    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
+        """rollout_into for a one-hidden-layer policy: the gs_rollout1_* entry of the same arguments."""
+        self._rollout(self.rollout1_entry, pm, buf, mode, rng_seed, counter0)
+
+    def one_launch_supported(self, dims) -> bool:
+        """Whether rollout_into() serves a two-hidden-layer policy of these dims (a host computation)."""
+        cap = self.one_launch_max_envs
+        if self.rollout_entry is None or (cap is not None and self.num_envs > int(cap)):
+            return False
+        v = ctypes.c_int()
+        check(lib.gs_rollout_env_supported(dims, int(self.env_kind), ctypes.byref(v)), "gs_rollout_env_supported")
+        return bool(v.value)
+
+    def one_launch_mlp1_supported(self, dims) -> bool:
+        """Whether rollout1_into() serves a one-hidden-layer policy of these dims (a host computation)."""
+        if self.rollout1_entry is None:
+            return False
+        v = ctypes.c_int()
+        check(lib.gs_rollout1_supported(dims, ctypes.byref(v)), "gs_rollout1_supported")
+        return bool(v.value)
+
 
 class DeviceSyntheticVecEnv(DeviceVecEnv):
-    """Device twin of gsamd.synthetic_env.SyntheticVecEnv (same hash, same episodes)."""
+    """Device twin of gsamd.synthetic_env.SyntheticVecEnv (same hash, same episodes).  Its entries
+    take a step count kept on the host (or the captured rollout's clock), so it writes out its own
+    three calls; there is no one-hidden-layer one-launch rollout."""
+
+    rollout_entry = "gs_rollout_synth"
 
     def __init__(self, n_envs, obs_dim, n_actions, episode_len=200, seed=42, truncate_every=0, env_offset=0,
                  reward=1.0, device="cuda"):
@@ -110,6 +186,11 @@ class DeviceSyntheticVecEnv(DeviceVecEnv):
                                    *self._episode_counters(), *self._row_args(buf)), "gs_rollout_synth")
         self.step_count += buf.T
 
+    def one_launch_supported(self, dims) -> bool:
+        v = ctypes.c_int()
+        check(lib.gs_rollout_synth_supported(dims, ctypes.byref(v)), "gs_rollout_synth_supported")
+        return bool(v.value)
+
 
 class DeviceCartPoleVecEnv(DeviceVecEnv):
     """CartPole-v1 on device (gymnasium 1.x dynamics restated in
@@ -117,6 +198,8 @@ class DeviceCartPoleVecEnv(DeviceVecEnv):
     episodes is unpinned (reset draws use a counter hash, not PCG64)."""
 
     env_kind = GS_ENV_CARTPOLE       # gs_rollout_env's kind: one-launch rollouts when the policy fits in LDS
+    entry_stem, rollout_entry, rollout1_entry = "cartpole", "gs_rollout_env", "gs_rollout1_env"
+    needs_actions = "CartPole dynamics need the step's actions"
 
     def __init__(self, n_envs, seed=42, env_offset=0, max_steps=500, wrappers=(), device="cuda", **_):
         """`wrappers` is the config's env_wrappers list: empty, or the reference's
@@ -131,60 +214,28 @@ class DeviceCartPoleVecEnv(DeviceVecEnv):
             raise ValueError(f"the device CartPole-v1 does not apply env_wrappers={self.wrappers!r} "
                              "(gsamd.config.resolve_cartpole_wrappers)")
         self.wrappers_c, self.prev_phi = None, None
-        if resolved:
+        if resolved:                             # the reward shaper rides along: the shaped entries
             kw = resolved[0][1]
             self.wrappers_c = CartPoleWrappers(1, int(kw["clip_potential"]), float(kw["angle_reward_scale"]),
                                                float(kw["position_reward_scale"]))
             self.prev_phi = torch.zeros(N, dtype=torch.float64, **z)
+            self.entry_stem = "cartpole_shaped"
+            self.rollout_entry, self.rollout1_entry = "gs_rollout_cartpole_shaped", "gs_rollout1_cartpole_shaped"
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)
 
-    def reset(self):
-        if self.wrappers_c is not None:
-            check(lib.gs_cartpole_shaped_reset(ptr(self.state), ptr(self.prev_phi), ptr(self.meta), ptr(self.ep_ret),
-                                               ptr(self.obs), self.wrappers_c, self.num_envs, self.seed,
-                                               self.env_offset, stream_handle()), "gs_cartpole_shaped_reset")
-            return self.obs, {}
-        check(lib.gs_cartpole_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.num_envs,
-                                    self.seed, self.env_offset, stream_handle()), "gs_cartpole_reset")
-        return self.obs, {}
+    @classmethod
+    def from_config(cls, c, kind, **kw):
+        """The env a config names (device_env_from_config; kw: the stage's seed, the rank's
+        env_offset, the device)."""
+        if _is_pixel(c) or c.resolved_obs_dim() != 4 or c.resolved_n_actions() != 2:
+            raise ValueError("env_dynamics='cartpole' needs vector observations of dim 4 and 2 actions")
+        # every stage's env carries the config's reward shaper (the reference builds each from the same list)
+        return cls(c.n_envs, max_steps=int(c.max_episode_steps or 500), wrappers=list(c.env_wrappers or ()), **kw)
 
-    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
-        if actions is None:
-            raise ValueError("CartPole dynamics need the step's actions")
-        if self.wrappers_c is not None:
-            check(lib.gs_cartpole_shaped_step(ptr(self.state), ptr(self.prev_phi), ptr(self.meta), ptr(self.ep_ret),
-                                              ptr(self.obs), self.wrappers_c, ptr(actions), self.num_envs,
-                                              self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                              ptr(dones_row), ptr(timeouts_row), *self._episode_counters(),
-                                              stream_handle()), "gs_cartpole_shaped_step")
-            return
-        check(lib.gs_cartpole_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), ptr(actions),
-                                   self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                   ptr(dones_row), ptr(timeouts_row), *self._episode_counters(), stream_handle()),
-              "gs_cartpole_step")
-
-    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
-        head = self._policy_args(pm, buf, mode, rng_seed, counter0)
-        tail = (self.max_steps, self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf))
-        if self.wrappers_c is not None:          # the reward shaper rides along
-            check(lib.gs_rollout_cartpole_shaped(*head, ptr(self.state), ptr(self.prev_phi), ptr(self.meta),
-                                                 ptr(self.ep_ret), ptr(self.obs), self.wrappers_c, *tail),
-                  "gs_rollout_cartpole_shaped")
-            return
-        check(lib.gs_rollout_env(*head, int(self.env_kind), ptr(self.state), ptr(self.meta), ptr(self.ep_ret),
-                                 ptr(self.obs), *tail), "gs_rollout_env")
-
-    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
-        """rollout_into for a one-hidden-layer policy: the gs_rollout1_* entry of the same arguments."""
-        head = self._policy_args(pm, buf, mode, rng_seed, counter0)
-        tail = (self.max_steps, self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf))
-        if self.wrappers_c is not None:
-            check(lib.gs_rollout1_cartpole_shaped(*head, ptr(self.state), ptr(self.prev_phi), ptr(self.meta),
-                                                  ptr(self.ep_ret), ptr(self.obs), self.wrappers_c, *tail),
-                  "gs_rollout1_cartpole_shaped")
-            return
-        check(lib.gs_rollout1_env(*head, int(self.env_kind), ptr(self.state), ptr(self.meta), ptr(self.ep_ret),
-                                  ptr(self.obs), *tail), "gs_rollout1_env")
+    def _env_args(self):
+        if self.wrappers_c is None:
+            return ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs)
+        return ptr(self.state), ptr(self.prev_phi), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.wrappers_c
 
 
 class DeviceAcrobotVecEnv(DeviceVecEnv):
@@ -193,6 +244,8 @@ class DeviceAcrobotVecEnv(DeviceVecEnv):
     Parity with gymnasium's own episodes is unpinned (reset draws use a counter hash, not PCG64)."""
 
     env_kind = GS_ENV_ACROBOT
+    entry_stem, rollout_entry, rollout1_entry = "acrobot", "gs_rollout_env", "gs_rollout1_env"
+    needs_actions = "Acrobot dynamics need the step's actions"
     # One-launch rollouts are the default only up to this many envs: past it the graph-replayed
     # step loop measured faster (DESIGN.md §4.1, profiles/acrobot_collect.json).  None = always.
     one_launch_max_envs = None
@@ -202,31 +255,14 @@ class DeviceAcrobotVecEnv(DeviceVecEnv):
         self.max_steps = int(max_steps)
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)      # theta1, theta2, omega1, omega2
 
-    def reset(self):
-        check(lib.gs_acrobot_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.num_envs,
-                                   self.seed, self.env_offset, stream_handle()), "gs_acrobot_reset")
-        return self.obs, {}
+    @classmethod
+    def from_config(cls, c, kind, **kw):
+        if _is_pixel(c) or c.resolved_obs_dim() != 6 or c.resolved_n_actions() != 3:
+            raise ValueError("env_dynamics='acrobot' needs vector observations of dim 6 and 3 actions")
+        return cls(c.n_envs, max_steps=int(c.max_episode_steps or 500), **kw)
 
-    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
-        if actions is None:
-            raise ValueError("Acrobot dynamics need the step's actions")
-        check(lib.gs_acrobot_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), ptr(actions),
-                                  self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                  ptr(dones_row), ptr(timeouts_row), *self._episode_counters(), stream_handle()),
-              "gs_acrobot_step")
-
-    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
-        check(lib.gs_rollout_env(*self._policy_args(pm, buf, mode, rng_seed, counter0), int(self.env_kind),
-                                 ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.max_steps,
-                                 self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf)),
-              "gs_rollout_env")
-
-    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
-        """rollout_into for a one-hidden-layer policy."""
-        check(lib.gs_rollout1_env(*self._policy_args(pm, buf, mode, rng_seed, counter0), int(self.env_kind),
-                                  ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.max_steps,
-                                  self.seed, self.env_offset, *self._episode_counters(), *self._row_args(buf)),
-              "gs_rollout1_env")
+    def _env_args(self):
+        return ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs)
 
 
 def mountaincar_wrappers_struct(wrappers) -> MountainCarWrappers:
@@ -263,6 +299,8 @@ class DeviceMountainCarVecEnv(DeviceVecEnv):
     (tests/golden/mountaincar_wrappers.npz).  The wrappers' info diagnostics are not reproduced."""
 
     env_kind = GS_ENV_MOUNTAINCAR
+    entry_stem, rollout_entry, rollout1_entry = "mountaincar", "gs_rollout_mountaincar", "gs_rollout1_mountaincar"
+    needs_actions = "MountainCar dynamics need the step's actions"
     # One-launch rollouts are the default only up to this many envs: past it the graph-replayed
     # step loop measured faster (DESIGN.md §4.1, profiles/mountaincar_collect.json).  None = always.
     one_launch_max_envs = None
@@ -277,37 +315,17 @@ class DeviceMountainCarVecEnv(DeviceVecEnv):
         self.state = torch.zeros(N, 4, dtype=torch.float64, **z)      # p, v, prev obs p, prev obs v
         self.counts = torch.zeros(N, cells, dtype=torch.int32, **z)
 
-    def _counts_ptr(self):
-        return ptr(self.counts) if self.counts.numel() else None
+    @classmethod
+    def from_config(cls, c, kind, **kw):
+        if _is_pixel(c) or c.resolved_obs_dim() != 2 or c.resolved_n_actions() != 3:
+            raise ValueError("env_dynamics='mountaincar' needs vector observations of dim 2 and 3 actions")
+        # every stage's env carries the config's wrappers (the reference builds each from the same list)
+        return cls(c.n_envs, max_steps=int(c.max_episode_steps or 200), wrappers=list(c.env_wrappers or ()), **kw)
 
-    def reset(self):
-        check(lib.gs_mountaincar_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs),
-                                       self._counts_ptr(), self.wrappers_c, self.num_envs, self.seed,
-                                       self.env_offset, stream_handle()), "gs_mountaincar_reset")
-        return self.obs, {}
-
-    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
-        if actions is None:
-            raise ValueError("MountainCar dynamics need the step's actions")
-        check(lib.gs_mountaincar_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs),
-                                      self._counts_ptr(), self.wrappers_c, ptr(actions), self.num_envs,
-                                      self.max_steps, self.seed, self.env_offset, ptr(rewards_row), ptr(dones_row),
-                                      ptr(timeouts_row), *self._episode_counters(), stream_handle()),
-              "gs_mountaincar_step")
-
-    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
-        """Its count tables and wrappers ride along."""
-        check(lib.gs_rollout_mountaincar(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
-                                         ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self._counts_ptr(),
-                                         self.wrappers_c, self.max_steps, self.seed, self.env_offset,
-                                         *self._episode_counters(), *self._row_args(buf)), "gs_rollout_mountaincar")
-
-    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
-        """rollout_into for a one-hidden-layer policy."""
-        check(lib.gs_rollout1_mountaincar(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
-                                          ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self._counts_ptr(),
-                                          self.wrappers_c, self.max_steps, self.seed, self.env_offset,
-                                          *self._episode_counters(), *self._row_args(buf)), "gs_rollout1_mountaincar")
+    def _env_args(self):
+        """Its count tables (NULL without a count bonus) and wrappers ride along."""
+        return (ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs),
+                ptr(self.counts) if self.counts.numel() else None, self.wrappers_c)
 
 
 class DeviceBanditVecEnv(DeviceVecEnv):
@@ -321,7 +339,9 @@ class DeviceBanditVecEnv(DeviceVecEnv):
     counter hash, not numpy's PCG64 ziggurat)."""
 
     env_kind = GS_ENV_BANDIT         # one-launch rollouts up to GS_BANDIT_ROLLOUT_MAX_ARMS arms
-    one_launch_max_envs = None
+    # (two hidden layers; the one-hidden-layer entry serves any n_arms the env takes)
+    entry_stem, rollout_entry, rollout1_entry = "bandit", "gs_rollout_bandit", "gs_rollout1_bandit"
+    needs_actions = "the bandit needs the step's actions"
 
     def __init__(self, n_envs, n_arms=10, means=None, stds=1.0, episode_length=1, seed=42, env_offset=0,
                  max_steps=None, device="cuda", **_):
@@ -343,31 +363,27 @@ class DeviceBanditVecEnv(DeviceVecEnv):
         for a in range(n):
             self.spec.means[a], self.spec.stds[a] = float(m[a]), float(s[a])
 
-    def reset(self):
-        check(lib.gs_bandit_reset(ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, self.num_envs,
-                                  stream_handle()), "gs_bandit_reset")
-        return self.obs, {}
+    @classmethod
+    def from_config(cls, c, kind, **kw):
+        b = resolve_bandit_env(c)
+        if _is_pixel(c) or b is None or c.resolved_n_actions() != b["n_arms"]:
+            raise ValueError("env_dynamics='bandit' needs env_id Bandit-v0 with env_kwargs the device applies "
+                             "(gsamd.config.resolve_bandit_env)")
+        if b["n_arms"] > BANDIT_MAX_TRAINABLE_ARMS:
+            # the env kernels take 32 arms; the two-hidden-layer update does not yet (measured at 20 arms:
+            # NaN / inf losses).  Its forward stages a 16-row tile's observations and the 16 x (A + 1) head
+            # weights with one element per thread of 256: complete only for obs_dim <= 16, n_actions <= 15.
+            raise ValueError(f"Bandit-v0 with n_arms={b['n_arms']}: the MLP update serves obs_dim <= 16 and "
+                             f"n_actions <= 15, so at most {BANDIT_MAX_TRAINABLE_ARMS} arms train on the device")
+        return cls(c.n_envs, n_arms=b["n_arms"], means=b["means"], stds=b["stds"], episode_length=b["episode_length"],
+                   max_steps=int(c.max_episode_steps or 0) or None, **kw)
 
-    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
-        if actions is None:
-            raise ValueError("the bandit needs the step's actions")
-        check(lib.gs_bandit_step(ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, ptr(actions),
-                                 self.num_envs, self.max_steps, self.seed, self.env_offset, ptr(rewards_row),
-                                 ptr(dones_row), ptr(timeouts_row), *self._episode_counters(), stream_handle()),
-              "gs_bandit_step")
+    def _env_args(self):
+        return ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec
 
-    def rollout_into(self, pm, buf, mode, rng_seed, counter0):
-        check(lib.gs_rollout_bandit(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.meta),
-                                    ptr(self.ep_ret), ptr(self.obs), self.spec, self.max_steps, self.seed,
-                                    self.env_offset, *self._episode_counters(), *self._row_args(buf)),
-              "gs_rollout_bandit")
-
-    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
-        """rollout_into for a one-hidden-layer policy (any n_arms the env takes)."""
-        check(lib.gs_rollout1_bandit(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.meta),
-                                     ptr(self.ep_ret), ptr(self.obs), self.spec, self.max_steps, self.seed,
-                                     self.env_offset, *self._episode_counters(), *self._row_args(buf)),
-              "gs_rollout1_bandit")
+    def _reset_args(self):
+        """A stateless env with no reset draw: gs_bandit_reset takes no seed and no offset."""
+        return (*self._env_args(), self.num_envs)
 
 
 class DeviceTabularVecEnv(DeviceVecEnv):
@@ -376,11 +392,14 @@ class DeviceTabularVecEnv(DeviceVecEnv):
     term, starts, n_states, n_actions, K) passed as `tables`.  The observation is the reference's
     DiscreteEncoder (`encoding` array / binary / onehot) of the state, as float32.  NEXT_STEP
     autoreset, TimeLimit `max_steps` (default: the registered id's, 100 / 200).  The tables are
-    uploaded once, here.  No env_kind (the two-hidden-layer one-launch rollout does not serve it):
+    uploaded once, here.  No rollout_entry (the two-hidden-layer one-launch rollout does not serve it):
     by default the collector replays its step graph; a one-hidden-layer policy's whole rollout is
     one launch through rollout1_into when the collector is built with one_launch_mlp1=True.
     Parity with gymnasium's own episodes is unpinned (the outcome and reset draws use the counter
     hash, not PCG64)."""
+
+    entry_stem, rollout1_entry = "tabular", "gs_rollout1_tabular"
+    needs_actions = "a tabular env needs the step's actions"
 
     def __init__(self, n_envs, kind="frozenlake", encoding="binary", map_name="4x4", is_slippery=True, seed=42,
                  env_offset=0, max_steps=None, tables=None, device="cuda", **_):
@@ -403,28 +422,53 @@ class DeviceTabularVecEnv(DeviceVecEnv):
                                 GS_ENCODINGS[self.encoding], self.obs_dim)
         self.state = torch.zeros(N, dtype=torch.int32, **z)
 
-    def reset(self):
-        check(lib.gs_tabular_reset(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
-                                   ptr(self.starts), self.num_envs, self.seed, self.env_offset, stream_handle()),
-              "gs_tabular_reset")
-        return self.obs, {}
+    @classmethod
+    def from_config(cls, c, kind, **kw):
+        tab = resolve_tabular_env(c)
+        if _is_pixel(c) or tab is None or tab["kind"] != kind:
+            raise ValueError(f"env_dynamics={kind!r} needs env_id FrozenLake-v1 / Taxi-v3 with exactly the "
+                             "DiscreteEncoder wrapper (gsamd.config.resolve_tabular_env)")
+        return cls(c.n_envs, kind=kind, encoding=tab["encoding"], map_name=tab["map_name"],
+                   is_slippery=tab["is_slippery"], max_steps=int(c.max_episode_steps or 0) or None, **kw)
 
-    def step_into(self, rewards_row, dones_row, timeouts_row, actions=None, clock=None, step=None):
-        if actions is None:
-            raise ValueError("a tabular env needs the step's actions")
-        check(lib.gs_tabular_step(ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
-                                  ptr(self.next_table), ptr(self.reward_table), ptr(self.term_table),
-                                  ptr(self.starts), ptr(actions), self.num_envs, self.max_steps, self.seed,
-                                  self.env_offset, ptr(rewards_row), ptr(dones_row), ptr(timeouts_row),
-                                  *self._episode_counters(), stream_handle()), "gs_tabular_step")
+    def _env_args(self):
+        return (ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, ptr(self.next_table),
+                ptr(self.reward_table), ptr(self.term_table), ptr(self.starts))
 
-    def rollout1_into(self, pm, buf, mode, rng_seed, counter0):
-        """The whole rollout of a one-hidden-layer policy in one launch (gs_rollout1_tabular)."""
-        check(lib.gs_rollout1_tabular(*self._policy_args(pm, buf, mode, rng_seed, counter0), ptr(self.state),
-                                      ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec,
-                                      ptr(self.next_table), ptr(self.reward_table), ptr(self.term_table),
-                                      ptr(self.starts), self.max_steps, self.seed, self.env_offset,
-                                      *self._episode_counters(), *self._row_args(buf)), "gs_rollout1_tabular")
+    def _reset_args(self):
+        """gs_tabular_reset draws a start state: the spec and starts, none of the three tables."""
+        return (ptr(self.state), ptr(self.meta), ptr(self.ep_ret), ptr(self.obs), self.spec, ptr(self.starts),
+                self.num_envs, self.seed, self.env_offset)
+
+
+# device_env_kind's strings -> the class that builds itself from the config (from_config); every other
+# string is the synthetic env's, or the Atari one's for rgb observations
+DEVICE_ENVS = {"cartpole": DeviceCartPoleVecEnv, "acrobot": DeviceAcrobotVecEnv, "mountaincar": DeviceMountainCarVecEnv,
+               "bandit": DeviceBanditVecEnv, **{kind: DeviceTabularVecEnv for kind in TABULAR_KINDS}}
+
+
+def device_env_from_config(c, stage, rank, device):
+    """The device env of config.device_env_kind for a stage ("train": the training seeds) and a
+    rank (its envs' offset); a config naming an env the device does not simulate raises."""
+    kind = device_env_kind(c)
+    if kind is None:
+        raise ValueError(
+            f"env_id {c.env_id!r} (obs_type {c.obs_type!r}) has no device dynamics: pass env=<the gymnasium "
+            f"VectorEnv build_env_from_config(config, seed=config.seed_train) returns> (or env_factory=), or "
+            f"set env_dynamics='synthetic' for the fixed-length synthetic env of the benchmark")
+    off = rank * c.n_envs
+    train = stage == "train"
+    if kind in DEVICE_ENVS:
+        return DEVICE_ENVS[kind].from_config(c, kind, seed=c.seed_train if train else c.seed_val, env_offset=off,
+                                             device=device)
+    seed = c.seed if train else c.seed + 1000
+    if _is_pixel(c):
+        return DeviceAtariVecEnv(n_envs=c.n_envs, n_actions=c.resolved_n_actions(), episode_len=c.episode_len,
+                                 seed=seed, truncate_every=c.truncate_every, env_offset=off,
+                                 frame_stack=int(c.frame_stack or 4), device=device)
+    return DeviceSyntheticVecEnv(n_envs=c.n_envs, obs_dim=c.resolved_obs_dim(), n_actions=c.resolved_n_actions(),
+                                 episode_len=c.episode_len, seed=seed, truncate_every=c.truncate_every,
+                                 env_offset=off, device=device)
 
 
 class DeviceRolloutBuffer:
@@ -571,7 +615,7 @@ class DeviceRolloutCollector:
         # env_kind; rows bit-identical to the step-wise loop)
         self.one_launch = bool(one_launch) and hasattr(policy_model, "dims") and \
             self._one_launch_supported(env, policy_model)
-        # opt-in: a one-hidden-layer policy on a device env with a rollout1_into runs the whole
+        # opt-in: a one-hidden-layer policy on a device env with a gs_rollout1_* entry runs the whole
         # rollout as one launch too (gs_rollout1_*: one thread per env; rows bit-identical to the
         # step-wise loop).  Off by default: such a policy then takes the step graph, as before.
         self.one_launch_mlp1 = bool(one_launch_mlp1) and not self.one_launch and hasattr(policy_model, "dims") and \
@@ -701,31 +745,23 @@ class DeviceRolloutCollector:
 
     @staticmethod
     def _one_launch_supported(env, pm) -> bool:
+        """A two-hidden-layer policy on a device env whose rollout_into serves its shape
+        (DeviceVecEnv.one_launch_supported)."""
         if getattr(pm, "valid_mask", 0):     # the one-launch rollouts have no masked head: step loop / step graph
             return False
-        v = ctypes.c_int()
-        if isinstance(env, DeviceSyntheticVecEnv):
-            check(lib.gs_rollout_synth_supported(pm.dims, ctypes.byref(v)), "gs_rollout_synth_supported")
-            return bool(v.value)
-        kind = getattr(env, "env_kind", None)
-        if kind is None or not getattr(env, "device_native", False):
-            return False
-        cap = getattr(env, "one_launch_max_envs", None)
-        if cap is not None and int(env.num_envs) > int(cap):
-            return False
-        check(lib.gs_rollout_env_supported(pm.dims, int(kind), ctypes.byref(v)), "gs_rollout_env_supported")
-        return bool(v.value)
+        if not (getattr(env, "device_native", False) and isinstance(env, DeviceVecEnv)):
+            return False                     # a host env, or the Atari env (it has no one-launch rollout)
+        return env.one_launch_supported(pm.dims)
 
     @staticmethod
     def _one_launch_mlp1_supported(env, pm) -> bool:
-        """A one-hidden-layer policy on a device env that has a rollout1_into, when
-        gs_rollout1_supported takes the shape; never for a masked policy (no masked head there)."""
-        if getattr(pm, "valid_mask", 0) or int(getattr(pm.dims, "hidden2", -1)) != 0 or not getattr(env, "device_native", False) or \
-                not hasattr(env, "rollout1_into"):
+        """A one-hidden-layer policy on a device env whose rollout1_into serves its shape
+        (DeviceVecEnv.one_launch_mlp1_supported); never for a masked policy (no masked head there)."""
+        if getattr(pm, "valid_mask", 0) or int(getattr(pm.dims, "hidden2", -1)) != 0:
             return False
-        v = ctypes.c_int()
-        check(lib.gs_rollout1_supported(pm.dims, ctypes.byref(v)), "gs_rollout1_supported")
-        return bool(v.value)
+        if not (getattr(env, "device_native", False) and isinstance(env, DeviceVecEnv)):
+            return False                     # a host env, or the Atari env (it has no one-launch rollout)
+        return env.one_launch_mlp1_supported(pm.dims)
 
     def _collect_one_launch(self, mode):
         """The T vector steps as one launch (policy act + env step per step, envs resident in
