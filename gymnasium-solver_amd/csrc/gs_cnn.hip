@@ -1599,11 +1599,23 @@ __device__ __forceinline__ float adam_flat(float g, float &m, float &v, float p,
     return p + aa.neg_step_size * (m / denom);
 }
 
+// the step of optimizer OPT on one parameter, g the clipped gradient: AdamW decays p first (gs_head.h
+// adamw_decay), then exactly adam_flat; SGD is p + f32(-lr) g and leaves m and v alone
+template <int OPT>
+__device__ __forceinline__ float opt_flat(float g, float &m, float &v, float p, const AdamArgs &aa)
+{
+    if constexpr (OPT == kOptSGD) return p + aa.neg_step_size * g;
+    else if constexpr (OPT == kOptAdamW) return adam_flat(g, m, v, adamw_decay(p, aa), aa);
+    else return adam_flat(g, m, v, p, aa);
+}
+
 // ---- clip coefficient from the partials (every block, fixed order) + Adam (torch single-tensor):
 // kAdamQuads float4 of parameters per thread, all loaded before the norm reduction (grid =
 // ceil(n / (1024 kAdamQuads)) + 1), the scalar tail by the last block
 // Pbf (bf16 trunk storage): the new parameters' bf16 copy (round to nearest even), the next
 // minibatch's weight operands
+// OPT: the optimizer (opt_flat); SGD issues no load or store of M / V
+template <int OPT>
 __global__ __launch_bounds__(256) void k_clip_adam_flat(float *__restrict__ Pm, float *__restrict__ G,
                                                         float *__restrict__ M, float *__restrict__ V, int64_t n,
                                                         const double *__restrict__ part, int nparts, AdamArgs aa,
@@ -1633,8 +1645,10 @@ __global__ __launch_bounds__(256) void k_clip_adam_flat(float *__restrict__ Pm, 
         g4[u] = m4[u] = v4[u] = p4[u] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (n4 > 0) {
             g4[u] = reinterpret_cast<const float4 *>(G)[ic];
-            m4[u] = reinterpret_cast<const float4 *>(M)[ic];
-            v4[u] = reinterpret_cast<const float4 *>(V)[ic];
+            if constexpr (OPT != kOptSGD) {
+                m4[u] = reinterpret_cast<const float4 *>(M)[ic];
+                v4[u] = reinterpret_cast<const float4 *>(V)[ic];
+            }
             p4[u] = reinterpret_cast<const float4 *>(Pm)[ic];
         }
     }
@@ -1681,10 +1695,12 @@ __global__ __launch_bounds__(256) void k_clip_adam_flat(float *__restrict__ Pm, 
         float m[4] = {m4[u].x, m4[u].y, m4[u].z, m4[u].w}, v[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w};
         float p[4] = {p4[u].x, p4[u].y, p4[u].z, p4[u].w};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) p[q] = adam_flat(g[q], m[q], v[q], p[q], aa);
+        for (int q = 0; q < 4; ++q) p[q] = opt_flat<OPT>(g[q], m[q], v[q], p[q], aa);
         reinterpret_cast<float4 *>(G)[i] = make_float4(g[0], g[1], g[2], g[3]);
-        reinterpret_cast<float4 *>(M)[i] = make_float4(m[0], m[1], m[2], m[3]);
-        reinterpret_cast<float4 *>(V)[i] = make_float4(v[0], v[1], v[2], v[3]);
+        if constexpr (OPT != kOptSGD) {
+            reinterpret_cast<float4 *>(M)[i] = make_float4(m[0], m[1], m[2], m[3]);
+            reinterpret_cast<float4 *>(V)[i] = make_float4(v[0], v[1], v[2], v[3]);
+        }
         reinterpret_cast<float4 *>(Pm)[i] = make_float4(p[0], p[1], p[2], p[3]);
         if (Pbf) reinterpret_cast<uint2 *>(Pbf)[i] = bf16x4_rne(p);
     }
@@ -1692,10 +1708,10 @@ __global__ __launch_bounds__(256) void k_clip_adam_flat(float *__restrict__ Pm, 
         for (int64_t k = 4 * n4 + threadIdx.x; k < n; k += 256) {
             const float g = G[k] * coef;
             G[k] = g;
-            float m = M[k], v = V[k];
-            Pm[k] = adam_flat(g, m, v, Pm[k], aa);
-            M[k] = m;
-            V[k] = v;
+            float m = 0.0f, v = 0.0f;
+            if constexpr (OPT != kOptSGD) m = M[k], v = V[k];
+            Pm[k] = opt_flat<OPT>(g, m, v, Pm[k], aa);
+            if constexpr (OPT != kOptSGD) M[k] = m, V[k] = v;
             if (Pbf) Pbf[k] = __builtin_bit_cast(uint16_t, (__bf16)Pm[k]);
         }
 }
@@ -2316,10 +2332,13 @@ int cnn_step(float *P, float *G, float *Mm, float *Vv, const CnnLayout &L, const
         hipLaunchKernelGGL(k_norm_partials, dim3(kNormBlocks), dim3(256), 0, s, G, L.P, w.norm_part, stop, L.oWf, L.oWp,
                            L.oWv);
     const unsigned nadam = (unsigned)((L.P / 4 + 256 * kAdamQuads - 1) / (256 * kAdamQuads) + 1);
-    hipLaunchKernelGGL(k_clip_adam_flat, dim3(nadam), dim3(256), 0, s, P, G, Mm, Vv, L.P, w.norm_part, kNormBlocks, aa,
-                       metrics, stop, xh ? w.pbf : nullptr, w.norm_part + 5 * kNormBlocks, nsum1);
-    GS_LAUNCH_CHECK("k_clip_adam_flat");
-    return GS_OK;
+    return with_opt(aa.opt, [&](auto opt) {
+        hipLaunchKernelGGL(k_clip_adam_flat<decltype(opt)::value>, dim3(nadam), dim3(256), 0, s, P, G, Mm, Vv, L.P,
+                           w.norm_part, kNormBlocks, aa, metrics, stop, xh ? w.pbf : nullptr,
+                           w.norm_part + 5 * kNormBlocks, nsum1);
+        GS_LAUNCH_CHECK("k_clip_adam_flat");
+        return (int)GS_OK;
+    });
 }
 
 
@@ -2435,6 +2454,7 @@ extern "C" int gs_cnn_ppo_update_global(float *params, float *grads, float *adam
                                         int64_t adam_step0, float *metrics, int32_t *stop_flag, void *workspace,
                                         gs_comm *comm, const gs_ppo_global *glob, void *stream)
 {
+    GS_REQUIRE_OPT_FLAGS(hp.flags, "gs_cnn_ppo_update_global");
     int rc = validate_cnn_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(n_minibatches >= 0 && adam_step0 >= 0, "bad n_minibatches/adam_step0");
@@ -2466,6 +2486,7 @@ extern "C" int gs_cnn_ppo_update(float *params, float *grads, float *adam_m, flo
                                  int64_t n_minibatches, int64_t adam_step0, float *metrics, int32_t *stop_flag,
                                  void *workspace, gs_comm *comm, void *stream)
 {
+    GS_REQUIRE_OPT_FLAGS(hp.flags, "gs_cnn_ppo_update");
     int rc = validate_cnn_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(n_minibatches >= 0 && adam_step0 >= 0, "bad n_minibatches/adam_step0");

@@ -1,6 +1,7 @@
 // Shared declarations for the libgsamd kernels (gfx950 / CDNA4, wave64).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -229,20 +230,26 @@ struct LossArgs {
     int bf16;                   // GS_HP_BF16: the fused MLP chain's MFMA operands in bf16
 };
 
+// the optimizer of a step (include/gsamd.h GS_HP_OPT_*): a template parameter of the step kernels
+constexpr int kOptAdam = 0, kOptAdamW = 1, kOptSGD = 2;
+
 struct AdamArgs {
     float max_norm;         // <= 0: no clip
     float one_minus_b1;     // lerp weight f32(1 - beta1)
     float b2;               // f32(beta2)
     float one_minus_b2;     // f32(1 - beta2)
-    float neg_step_size;    // f32(-lr / (1 - beta1^t))
+    float neg_step_size;    // f32(-lr / (1 - beta1^t)); SGD: f32(-lr)
     float bc2_sqrt;         // f32(sqrt(1 - beta2^t))
     float inv_bc2_sqrt;     // f32(1 / sqrt(1 - beta2^t)) (MLP chain: a multiply instead of a division)
     float eps;
     float grad_scale;       // 1/world for all-reduced sums, else 1
     int n_slots;
     int nrb;                // dW1/db1 partial row blocks (0: grads already final in G)
+    int opt;                // kOptAdam / kOptAdamW / kOptSGD (here and in decay's place the struct had padding:
+                            // no other field moves)
     const float *sched;     // optional device table {neg_step_size, inv_bc2_sqrt} per step (graph replay)
     int sched_idx;
+    float decay;            // AdamW: f32(1 - (double)lr * GS_ADAMW_WEIGHT_DECAY), else 1
     const int64_t *step_base;   // graph chunk replay: added to sched_idx and the metrics record
     int stage_lds;          // set by the launcher: stage slots + partials through LDS
     // fused update: the step's squared pre-clip norm x grad_scale^2 in double, for k_metrics_all's
@@ -250,6 +257,9 @@ struct AdamArgs {
     // k_clip_adam: offset to its step like its metrics record (+ *step_base in a replay)
     double *normsq;
 };
+// the lagged forward takes the struct inside its kernel arguments: opt and decay sit in what was padding
+static_assert(sizeof(AdamArgs) == 88 && offsetof(AdamArgs, sched) == 48 && offsetof(AdamArgs, step_base) == 64,
+              "AdamArgs: the kernel-argument offsets of the Adam fields stay where they were");
 
 // Lagged optimizer step of the single-GPU fused chain (gs_ppo_update): the forward of
 // minibatch k first applies minibatch k-1's clip + Adam step to the parameters it reads

@@ -91,6 +91,47 @@ __device__ __forceinline__ float adam_param(float graw, float coef, float &m, fl
     return g;
 }
 
+// torch.optim.AdamW's decoupled decay of one parameter, ahead of Adam's step: p.mul_(1 - lr * weight_decay)
+// with the factor formed on the host (AdamArgs::decay).  __fmul_rn: one rounding of its own in the
+// files that contract a mul + add too, so a parameter with a zero gradient is p * d bit for bit everywhere.
+__device__ __forceinline__ float adamw_decay(float p, const AdamArgs &aa) { return __fmul_rn(p, aa.decay); }
+
+// One parameter of torch.optim.AdamW (single-tensor path): the decay, then exactly adam_param.
+__device__ __forceinline__ float adamw_param(float graw, float coef, float &m, float &v, float &p,
+                                             const AdamArgs &aa, float neg_step, float inv_bc2s)
+{
+    p = adamw_decay(p, aa);
+    return adam_param(graw, coef, m, v, p, aa, neg_step, inv_bc2s);
+}
+
+// One parameter of torch.optim.SGD (no momentum, no decay) on the clipped gradient:
+// p.add_(grad, alpha=-lr); aa.neg_step_size is f32(-lr), no moment and no schedule entry is read.
+__device__ __forceinline__ float sgd_param(float graw, float coef, float &p, const AdamArgs &aa)
+{
+    const float g = graw * coef;
+    p = p + aa.neg_step_size * g;
+    return g;
+}
+
+// The step of optimizer OPT (kOptAdam / kOptAdamW / kOptSGD) on one parameter; SGD leaves m and v alone.
+template <int OPT>
+__device__ __forceinline__ float opt_param(float graw, float coef, float &m, float &v, float &p, const AdamArgs &aa,
+                                           float neg_step, float inv_bc2s)
+{
+    if constexpr (OPT == kOptSGD) return sgd_param(graw, coef, p, aa);
+    else if constexpr (OPT == kOptAdamW) return adamw_param(graw, coef, m, v, p, aa, neg_step, inv_bc2s);
+    else return adam_param(graw, coef, m, v, p, aa, neg_step, inv_bc2s);
+}
+
+// host: call f with the optimizer of a step as a compile-time constant
+template <class F>
+inline int with_opt(int opt, F &&f)
+{
+    if (opt == kOptSGD) return f(std::integral_constant<int, kOptSGD>{});
+    if (opt == kOptAdamW) return f(std::integral_constant<int, kOptAdamW>{});
+    return f(std::integral_constant<int, kOptAdam>{});
+}
+
 // ------------------------------------------------------------------------------------
 // per-row categorical head math shared by rollout and loss kernels
 // ------------------------------------------------------------------------------------

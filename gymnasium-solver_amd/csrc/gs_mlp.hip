@@ -2779,7 +2779,8 @@ void k_bwd_chain(const float *__restrict__ P, const float *__restrict__ h1,
 // (float4 loads / stores of p, g, m, v), the partials go straight to registers as float4
 // with every load in flight at once, are folded there in row-block order, and only the folded
 // values pass through LDS.  The generic variant (NRB == 0) stages the partials in LDS.
-template <class S, int NRB, int NQ>
+// OPT: the optimizer (gs_head.h opt_param).  SGD issues no load or store of M / V and reads no schedule entry.
+template <class S, int NRB, int NQ, int OPT = kOptAdam>
 __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layout Lrt, float *__restrict__ G,
                                                    float *__restrict__ M, float *__restrict__ V,
                                                    const float *__restrict__ part1, const float *__restrict__ sumsq,
@@ -2815,8 +2816,11 @@ __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layou
         const bool full = p0 + 3 < L.P;
         if (full) {
             const float4 g4 = p0 >= L.oW2 ? *reinterpret_cast<const float4 *>(G + p0) : make_float4(0.f, 0.f, 0.f, 0.f);
-            const float4 m4 = *reinterpret_cast<const float4 *>(M + p0);
-            const float4 v4 = *reinterpret_cast<const float4 *>(V + p0);
+            float4 m4 = make_float4(0.f, 0.f, 0.f, 0.f), v4 = m4;
+            if constexpr (OPT != kOptSGD) {
+                m4 = *reinterpret_cast<const float4 *>(M + p0);
+                v4 = *reinterpret_cast<const float4 *>(V + p0);
+            }
             const float4 q4 = *reinterpret_cast<const float4 *>(Pm + p0);
             gv[0] = g4.x, gv[1] = g4.y, gv[2] = g4.z, gv[3] = g4.w;
             mv[0] = m4.x, mv[1] = m4.y, mv[2] = m4.z, mv[3] = m4.w;
@@ -2828,8 +2832,8 @@ __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layou
                 const int64_t p = p0 + i;
                 const bool ok = p < L.P;
                 gv[i] = ok && p >= L.oW2 ? G[p] : 0.0f;
-                mv[i] = ok ? M[p] : 0.0f;
-                vv[i] = ok ? V[p] : 0.0f;
+                mv[i] = OPT != kOptSGD && ok ? M[p] : 0.0f;
+                vv[i] = OPT != kOptSGD && ok ? V[p] : 0.0f;
                 pv[i] = ok ? Pm[p] : 0.0f;
             }
         }
@@ -2902,8 +2906,8 @@ __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layou
                 }
             }
             gv[j] = g;
-            mv[j] = ok ? M[p] : 0.0f;
-            vv[j] = ok ? V[p] : 0.0f;
+            mv[j] = OPT != kOptSGD && ok ? M[p] : 0.0f;
+            vv[j] = OPT != kOptSGD && ok ? V[p] : 0.0f;
             pv[j] = ok ? Pm[p] : 0.0f;
         }
         // global squared norm (same order in every workgroup -> identical coef); the
@@ -2956,13 +2960,14 @@ __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layou
     }
     __syncthreads();
     const float coef = s_coef * aa.grad_scale;
-    const float neg_step = aa.sched ? aa.sched[2 * (aa.sched_idx + kb)] : aa.neg_step_size;
-    const float bc2s = aa.sched ? aa.sched[2 * (aa.sched_idx + kb) + 1] : aa.inv_bc2_sqrt;
+    const bool tab = OPT != kOptSGD && aa.sched;
+    const float neg_step = tab ? aa.sched[2 * (aa.sched_idx + kb)] : aa.neg_step_size;
+    const float bc2s = tab ? aa.sched[2 * (aa.sched_idx + kb) + 1] : aa.inv_bc2_sqrt;
     float go[4], mo[4], vo[4], po[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         float m = mv[j], v = vv[j], p = pv[j];
-        go[j] = adam_param(gv[j], coef, m, v, p, aa, neg_step, bc2s);
+        go[j] = opt_param<OPT>(gv[j], coef, m, v, p, aa, neg_step, bc2s);
         mo[j] = m;
         vo[j] = v;
         po[j] = p;
@@ -2970,8 +2975,10 @@ __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layou
     if (NRB > 0 && p0 + 3 < L.P) {
         *reinterpret_cast<float4 *>(G + p0) = make_float4(go[0], go[1], go[2], go[3]);
         *reinterpret_cast<float4 *>(Pm + p0) = make_float4(po[0], po[1], po[2], po[3]);
-        *reinterpret_cast<float4 *>(M + p0) = make_float4(mo[0], mo[1], mo[2], mo[3]);
-        *reinterpret_cast<float4 *>(V + p0) = make_float4(vo[0], vo[1], vo[2], vo[3]);
+        if constexpr (OPT != kOptSGD) {
+            *reinterpret_cast<float4 *>(M + p0) = make_float4(mo[0], mo[1], mo[2], mo[3]);
+            *reinterpret_cast<float4 *>(V + p0) = make_float4(vo[0], vo[1], vo[2], vo[3]);
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -2979,8 +2986,10 @@ __global__ __launch_bounds__(256) void k_clip_adam(float *__restrict__ Pm, Layou
             if (p >= L.P) break;
             G[p] = go[j];
             Pm[p] = po[j];
-            M[p] = mo[j];
-            V[p] = vo[j];
+            if constexpr (OPT != kOptSGD) {
+                M[p] = mo[j];
+                V[p] = vo[j];
+            }
         }
     }
     GS_STAMP_END(3)
@@ -3331,19 +3340,25 @@ int launch_clip_adam(float *P, const Layout &L, float *G, float *M, float *V, co
         const int nq = (int)((n1 / 4 + 255) / 256);
         const bool vec = aa.stage_lds && n1 % 4 == 0 && L.oW2 % 4 == 0 && al && aa.n_slots <= 512 && nq <= 2;
         using Sh = decltype(sh);
-        const void *fn = nullptr;   // the fused shapes: C2 (B 256 -> 8 row blocks), C3 (B 64 -> 2)
-        if (vec && aa.nrb == 8) fn = nq == 2 ? (const void *)k_clip_adam<Sh, 8, 2> : (const void *)k_clip_adam<Sh, 8, 1>;
-        if (vec && aa.nrb == 4) fn = nq == 2 ? (const void *)k_clip_adam<Sh, 4, 2> : (const void *)k_clip_adam<Sh, 4, 1>;
-        if (vec && aa.nrb == 2) fn = nq == 2 ? (const void *)k_clip_adam<Sh, 2, 2> : (const void *)k_clip_adam<Sh, 2, 1>;
-        if (fn) {
-            void *args[] = {&P, (void *)&L, &G, &M, &V, &part1, &sumsq, &aa, &metrics, &stop};
-            GS_HIP(hipLaunchKernel(fn, dim3(nblk), dim3(256), args, stage, s));
-        } else {
-            hipLaunchKernelGGL((k_clip_adam<Sh, 0, 0>), dim3(nblk), dim3(256), aa.stage_lds ? stage : 0, s, P, L, G,
-                               M, V, part1, sumsq, aa, metrics, stop);
-        }
-        GS_LAUNCH_CHECK("k_clip_adam");
-        return GS_OK;
+        return with_opt(aa.opt, [&](auto opt) {
+            constexpr int OPT = decltype(opt)::value;
+            const void *fn = nullptr;   // the fused shapes: C2 (B 256 -> 8 row blocks), C3 (B 64 -> 2)
+            if (vec && aa.nrb == 8)
+                fn = nq == 2 ? (const void *)k_clip_adam<Sh, 8, 2, OPT> : (const void *)k_clip_adam<Sh, 8, 1, OPT>;
+            if (vec && aa.nrb == 4)
+                fn = nq == 2 ? (const void *)k_clip_adam<Sh, 4, 2, OPT> : (const void *)k_clip_adam<Sh, 4, 1, OPT>;
+            if (vec && aa.nrb == 2)
+                fn = nq == 2 ? (const void *)k_clip_adam<Sh, 2, 2, OPT> : (const void *)k_clip_adam<Sh, 2, 1, OPT>;
+            if (fn) {
+                void *args[] = {&P, (void *)&L, &G, &M, &V, &part1, &sumsq, &aa, &metrics, &stop};
+                GS_HIP(hipLaunchKernel(fn, dim3(nblk), dim3(256), args, stage, s));
+            } else {
+                hipLaunchKernelGGL((k_clip_adam<Sh, 0, 0, OPT>), dim3(nblk), dim3(256), aa.stage_lds ? stage : 0, s, P,
+                                   L, G, M, V, part1, sumsq, aa, metrics, stop);
+            }
+            GS_LAUNCH_CHECK("k_clip_adam");
+            return (int)GS_OK;
+        });
     });
 }
 

@@ -236,7 +236,8 @@ __global__ __launch_bounds__(kRollout1Envs) void k_rollout1(const float *__restr
 // ------------------------------------------------------------------------------------
 // k_update1: all n minibatch steps of an update in one workgroup (file header).
 // ------------------------------------------------------------------------------------
-template <int AMAX>
+// OPT: the optimizer of the steps (gs_head.h opt_param); SGD stages no moments into LDS and leaves a.M / a.V alone
+template <int AMAX, int OPT = kOptAdam>
 __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
 {
     extern __shared__ double lds_d[];
@@ -266,10 +267,11 @@ __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
     const LossArgs &la = a.la;
     const bool kl_on = la.target_kl > 0.0f && a.stop != nullptr;
     const bool train = !a.loss_only;
+    constexpr bool kMoments = OPT != kOptSGD;
     // ---- prologue: the optimizer state into LDS, once
     for (int p = tid; p < NP; p += 256) {
         Ps[p] = a.P[p];
-        if (train) {
+        if (kMoments && train) {
             Ms[p] = a.M[p];
             Vs[p] = a.V[p];
         }
@@ -456,10 +458,10 @@ __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
             const float neg_step = (float)(-a.lr / bc1);
             const float inv_bc2s = (float)(1.0 / sqrt(bc2));
             for (int p = tid; p < NP; p += 256) {
-                float m = Ms[p], v = Vs[p], w = Ps[p];
-                const float g = adam_param(Gs[p], coef, m, v, w, a.aa, neg_step, inv_bc2s);
-                Ms[p] = m;
-                Vs[p] = v;
+                float m = 0.0f, v = 0.0f, w = Ps[p];
+                if constexpr (kMoments) m = Ms[p], v = Vs[p];
+                const float g = opt_param<OPT>(Gs[p], coef, m, v, w, a.aa, neg_step, inv_bc2s);
+                if constexpr (kMoments) Ms[p] = m, Vs[p] = v;
                 Ps[p] = w;
                 Gs[p] = g;
                 if (kl_on) a.G[p] = g;      // a later minibatch may trip the stop: keep the last applied one
@@ -490,8 +492,10 @@ __global__ __launch_bounds__(256) void k_update1(Layout1 L, Upd1Args a)
     if (train) {
         for (int p = tid; p < NP; p += 256) {
             a.P[p] = Ps[p];
-            a.M[p] = Ms[p];
-            a.V[p] = Vs[p];
+            if constexpr (kMoments) {
+                a.M[p] = Ms[p];
+                a.V[p] = Vs[p];
+            }
             if (!kl_on) a.G[p] = Gs[p];     // the last minibatch's clipped gradient
         }
         if (kl_on && tid == 0 && s_stop) *a.stop = 1;
@@ -643,6 +647,7 @@ int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const
                 const gs_ppo_hparams &hp, const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n,
                 int64_t adam_step0, float *metrics, int32_t *stop_flag, bool loss_only, hipStream_t s)
 {
+    if (!loss_only) GS_REQUIRE_OPT_FLAGS(hp.flags, "one-hidden-layer update");
     int rc = mlp1_check_dims(d);
     if (rc) return rc;
     GS_REQUIRE(!(hp.flags & GS_HP_BF16), "precision bf16 is a mode of the two-hidden-layer fused chain; a policy with "
@@ -679,11 +684,14 @@ int mlp1_update(float *params, float *grads, float *adam_m, float *adam_v, const
     const size_t lds = mlp1_update_lds_bytes(d);
     return with_amax(L.A, [&](auto amax) {
         constexpr int AMAX = decltype(amax)::value;
-        const int rl = set_lds_limit((const void *)k_update1<AMAX>, lds);
-        if (rl) return rl;
-        hipLaunchKernelGGL(k_update1<AMAX>, dim3(1), dim3(256), lds, s, L, a);
-        GS_LAUNCH_CHECK("k_update1");
-        return (int)GS_OK;
+        return with_opt(loss_only ? kOptAdam : a.aa.opt, [&](auto opt) {
+            constexpr int OPT = decltype(opt)::value;
+            const int rl = set_lds_limit((const void *)k_update1<AMAX, OPT>, lds);
+            if (rl) return rl;
+            hipLaunchKernelGGL((k_update1<AMAX, OPT>), dim3(1), dim3(256), lds, s, L, a);
+            GS_LAUNCH_CHECK("k_update1");
+            return (int)GS_OK;
+        });
     });
 }
 

@@ -249,6 +249,9 @@ __global__ void __launch_bounds__(256) k_pg_rows(Layout L, PgRowArgs a)
     rows_store_sums(acc, rsum, a.msums + (size_t)blockIdx.x * kPgSums);
 }
 
+// OPT: the optimizer of the step (gs_head.h opt_param); SGD touches neither M nor V.  The value head
+// (p >= nW) takes no step under any of them: the loss never reaches it, its .grad is None in the reference
+template <int OPT>
 __global__ void __launch_bounds__(256) k_pg_step(Layout L, PgStepArgs a)
 {
     __shared__ double red[2 * (256 + 16)];
@@ -314,9 +317,11 @@ __global__ void __launch_bounds__(256) k_pg_step(Layout L, PgStepArgs a)
     if (!a.do_step) return;
     const float coef = clip_coef(total, a.aa);
     for (int p = tid; p < nW; p += 256) {
-        float mm = a.M[p], vv = a.V[p], pp = a.P[p];
-        adam_param(a.G[p], coef, mm, vv, pp, a.aa, a.aa.neg_step_size, a.aa.inv_bc2_sqrt);
-        a.M[p] = mm, a.V[p] = vv, a.P[p] = pp;
+        float mm = 0.0f, vv = 0.0f, pp = a.P[p];
+        if constexpr (OPT != kOptSGD) mm = a.M[p], vv = a.V[p];
+        opt_param<OPT>(a.G[p], coef, mm, vv, pp, a.aa, a.aa.neg_step_size, a.aa.inv_bc2_sqrt);
+        if constexpr (OPT != kOptSGD) a.M[p] = mm, a.V[p] = vv;
+        a.P[p] = pp;
     }
 }
 
@@ -358,6 +363,7 @@ int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_m
            const gs_rollout_view &ro, const int32_t *idx, int64_t batch, int64_t n, int64_t adam_step0, float *metrics,
            void *workspace, size_t workspace_bytes, bool do_step, hipStream_t s, const char *what)
 {
+    if (do_step) GS_REQUIRE_OPT_FLAGS(hp.flags, what);
     int rc = pg_check_dims(dims);
     if (rc) return rc;
     GS_REQUIRE(!(hp.flags & GS_HP_BF16), "%s: precision bf16 is a mode of the PPO chain; the REINFORCE update is fp32 "
@@ -405,9 +411,14 @@ int pg_run(float *params, float *grads, float *adam_m, float *adam_v, const gs_m
         sa.do_step = do_step ? 1 : 0;
         sa.ent_coef = hp.ent_coef;
         if (do_step)
-            sa.aa = adam_args(hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps, hp.max_grad_norm, adam_step0 + k + 1);
-        hipLaunchKernelGGL(k_pg_step, dim3(step_groups), dim3(256), 0, s, L, sa);
-        GS_LAUNCH_CHECK("k_pg_step");
+            sa.aa = adam_args(hp.lr, hp.adam_beta1, hp.adam_beta2, hp.adam_eps, hp.max_grad_norm, adam_step0 + k + 1,
+                              hp.flags);
+        rc = with_opt(sa.aa.opt, [&](auto opt) {
+            hipLaunchKernelGGL(k_pg_step<decltype(opt)::value>, dim3(step_groups), dim3(256), 0, s, L, sa);
+            GS_LAUNCH_CHECK("k_pg_step");
+            return (int)GS_OK;
+        });
+        if (rc) return rc;
     }
     return GS_OK;
 }

@@ -588,6 +588,7 @@ extern "C" int gs_ppo_minibatch_step(float *params, float *grads, float *adam_m,
                                      int64_t adam_step, float *metrics, int32_t *stop_flag, void *workspace,
                                      gs_comm *comm, void *stream)
 {
+    GS_REQUIRE_OPT_FLAGS(hp.flags, "gs_ppo_minibatch_step");
     if (one_layer(dims)) {      // the one-launch update with n = 1
         GS_REQUIRE(!comm, "gs_ppo_minibatch_step: no gradient exchange for a policy with one hidden layer");
         GS_REQUIRE(adam_step >= 1, "adam_step is 1-based");
@@ -645,6 +646,8 @@ extern "C" int gs_ppo_stage(int stage, float *params, float *grads, float *adam_
                             int64_t adam_step, float *metrics, void *workspace, void *stream)
 {
     GS_REFUSE_ONE_LAYER(dims, "gs_ppo_stage");
+    GS_REQUIRE(!(hp.flags & (GS_HP_OPT_ADAMW | GS_HP_OPT_SGD)), "gs_ppo_stage: the optimizer bits GS_HP_OPT_ADAMW / "
+               "GS_HP_OPT_SGD are refused: the stages are the Adam chain's");
     int rc = validate_update(dims, ro, batch, workspace);
     if (rc) return rc;
     GS_REQUIRE(stage >= 0 && stage <= 7, "gs_ppo_stage: stage %d not in [0, 7]", stage);
@@ -743,7 +746,8 @@ int64_t g_graph_captures = 0;
 void baked_hparam_bits(const gs_ppo_hparams &hp, uint32_t (&out)[12])
 {
     gs_ppo_hparams h = hp;
-    h.lr = 0.0f;
+    // AdamW's decay factor and SGD's step size come from lr and are kernel arguments: baked too
+    if (opt_kind(hp.flags) == kOptAdam) h.lr = 0.0f;
     memcpy(out, &h, sizeof(out));
 }
 
@@ -755,6 +759,7 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
                       void *workspace, size_t workspace_bytes, gs_comm *comm, int use_graph, void *stream,
                       const gs_ppo_global *glob)
 {
+    GS_REQUIRE_OPT_FLAGS(hp.flags, glob ? "gs_ppo_update_global" : "gs_ppo_update");
     if (one_layer(dims)) {      // one launch of one workgroup for all the steps (use_graph: nothing to capture)
         GS_REQUIRE(!comm, "gs_ppo_update: no gradient exchange for a policy with one hidden layer");
         return mlp1_update(params, grads, adam_m, adam_v, dims, hp, ro, idx, batch, n_minibatches, adam_step0, metrics,
@@ -813,7 +818,9 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
     // minibatch k's clip + Adam runs inside the forward of k+1 (enqueue_step_lagged), with or
     // without a communicator; step 0's forward reads set 1, which starts as a copy of the
     // caller's parameters
-    const bool lagged = fused && lagged_enabled() && has_lagged(L, batch);
+    // AdamW / SGD (GS_HP_OPT_*): the fused chain with k_clip_adam of that kind per minibatch; the lagged forward is Adam's
+    const int kind = opt_kind(hp.flags);
+    const bool lagged = fused && lagged_enabled() && has_lagged(L, batch) && kind == kOptAdam;
     // GS_BWD_NT=256 in the environment runs the single-GPU chain's backward with four waves per workgroup
     // (the k_bwd body: bit-identical, slower on MI355X); a captured graph holds one of the two
     const int bwd_nt = bwd_chain_threads();
@@ -904,7 +911,8 @@ static int ppo_update(float *params, float *grads, float *adam_m, float *adam_v,
     BwdXchg bx_key;
     const bool in_bwd = comm && bwd_exchange_of(comm, L, batch, &bx_key);
     key.n[4] = (int64_t)(intptr_t)stop_flag ^ ((int64_t)(intptr_t)comm << 1) ^ (fused ? 1 : 0) ^
-               ((int64_t)lagged << 62) ^ ((int64_t)in_bwd << 61) ^ ((int64_t)(fused && bwd_nt == 256) << 60);
+               ((int64_t)lagged << 62) ^ ((int64_t)in_bwd << 61) ^ ((int64_t)(fused && bwd_nt == 256) << 60) ^
+               ((int64_t)kind << 58);
     key.n[5] = ro.T * 1000003 + ro.N + (glob ? glob->batch_global << 40 : 0);
     uint32_t hbits[12];
     baked_hparam_bits(hp, hbits);

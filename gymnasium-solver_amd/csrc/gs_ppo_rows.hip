@@ -494,6 +494,8 @@ __global__ void __launch_bounds__(256) k_ppo_rows_sum(RowsLayout L, RowsStepArgs
     if (tid < 3) a.normparts[3 * blockIdx.x + tid] = sq[tid];
 }
 
+// OPT: the optimizer of the step (gs_head.h opt_param); SGD touches neither M nor V
+template <int OPT>
 __global__ void __launch_bounds__(256) k_ppo_rows_step(RowsLayout L, RowsStepArgs a)
 {
     __shared__ double tot[16];
@@ -560,9 +562,11 @@ __global__ void __launch_bounds__(256) k_ppo_rows_step(RowsLayout L, RowsStepArg
     if (!a.do_step || tripped) return;
     const float coef = clip_coef(total, a.aa);
     for (int p = blockIdx.x * 256 + tid; p < L.P; p += gridDim.x * 256) {
-        float mm = a.M[p], vv = a.V[p], pp = a.P[p];
-        a.G[p] = adam_param(a.G[p], coef, mm, vv, pp, a.aa, a.aa.neg_step_size, a.aa.inv_bc2_sqrt);
-        a.M[p] = mm, a.V[p] = vv, a.P[p] = pp;
+        float mm = 0.0f, vv = 0.0f, pp = a.P[p];
+        if constexpr (OPT != kOptSGD) mm = a.M[p], vv = a.V[p];
+        a.G[p] = opt_param<OPT>(a.G[p], coef, mm, vv, pp, a.aa, a.aa.neg_step_size, a.aa.inv_bc2_sqrt);
+        if constexpr (OPT != kOptSGD) a.M[p] = mm, a.V[p] = vv;
+        a.P[p] = pp;
     }
 }
 
@@ -620,6 +624,7 @@ int rows_run(float *params, float *grads, float *adam_m, float *adam_v, const gs
              int32_t *stop_flag, void *workspace, size_t workspace_bytes, bool do_step, hipStream_t s, const char *what,
              uint32_t valid_mask = 0u)
 {
+    if (do_step) GS_REQUIRE_OPT_FLAGS(hp.flags, what);
     int rc = rows_check_dims(dims, what);
     if (rc) return rc;
     // the shift is undefined at 32 actions, where every bit names an action
@@ -693,8 +698,13 @@ int rows_run(float *params, float *grads, float *adam_m, float *adam_v, const gs
         if (do_step) sa.aa = adam_args(hp, adam_step0 + k + 1);
         hipLaunchKernelGGL(k_ppo_rows_sum, dim3((unsigned)ws.nsum), dim3(256), 0, s, L, sa);
         GS_LAUNCH_CHECK("k_ppo_rows_sum");
-        hipLaunchKernelGGL(k_ppo_rows_step, dim3(do_step ? (unsigned)ws.nsum : 1u), dim3(256), 0, s, L, sa);
-        GS_LAUNCH_CHECK("k_ppo_rows_step");
+        rc = with_opt(sa.aa.opt, [&](auto opt) {
+            hipLaunchKernelGGL(k_ppo_rows_step<decltype(opt)::value>, dim3(do_step ? (unsigned)ws.nsum : 1u), dim3(256), 0,
+                               s, L, sa);
+            GS_LAUNCH_CHECK("k_ppo_rows_step");
+            return (int)GS_OK;
+        });
+        if (rc) return rc;
     }
     return GS_OK;
 }

@@ -93,6 +93,10 @@ class PGHparams(ctypes.Structure):
 GS_MC_RTG, GS_MC_EPISODE = 0, 1     # include/gsamd.h: gs_mc_returns_f32 kinds
 GS_HP_BF16 = 1      # include/gsamd.h: bf16 MFMA operands in the NatureCNN update
 GS_HP_ACT_STATS = 2  # include/gsamd.h: per-minibatch activation statistics into the records (GS_M_ACT)
+GS_HP_OPT_ADAMW = 4  # include/gsamd.h: torch.optim.AdamW's step (decoupled decay GS_ADAMW_WEIGHT_DECAY); neither bit: Adam
+GS_HP_OPT_SGD = 8    # include/gsamd.h: torch.optim.SGD's step (no momentum, no decay)
+GS_ADAMW_WEIGHT_DECAY = 0.01
+OPT_FLAGS = {"adam": 0, "adamw": GS_HP_OPT_ADAMW, "sgd": GS_HP_OPT_SGD}   # config.optimizer -> the flags bit
 
 
 class RolloutView(ctypes.Structure):

@@ -26,6 +26,10 @@ import yaml
 from .presets import MODEL_REGISTRY, PRESETS
 
 
+# the optimizers of utils/optimizer_factory.py:6-29, each at torch's defaults but lr (include/gsamd.h GS_HP_OPT_*)
+OPTIMIZERS = ("adam", "adamw", "sgd")
+
+
 @dataclass
 class PPOConfig:
     env_id: str = ""
@@ -123,6 +127,11 @@ class PPOConfig:
         self.batch_size = int(self.batch_size)
 
     def validate(self):
+        # utils/optimizer_factory.py:6-29: a name or an enum-like with .value, case-insensitive
+        opt = str(getattr(self.optimizer, "value", self.optimizer)).lower()
+        if opt not in OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of 'adam', 'adamw' or 'sgd', got {self.optimizer!r}")
+        self.optimizer = opt
         for k in ("n_envs", "n_steps", "batch_size", "n_epochs", "policy_lr"):
             if getattr(self, k) is not None and getattr(self, k) <= 0:
                 raise ValueError(f"{k} must be positive, got {getattr(self, k)}")

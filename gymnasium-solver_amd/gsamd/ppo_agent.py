@@ -8,7 +8,7 @@ agents/ppo/ppo_agent.py:10-152):
   on_train_epoch_start()                      re-collect from epoch 1 on             (base_agent.py:284-328)
   training_step(batch, batch_idx)             one fused minibatch step               (base_agent.py:330-366)
   losses_for_batch(batch, batch_idx)          {loss, early_stop_epoch}               (ppo_agent.py:21-152)
-  configure_optimizers()                      Adam(lr=policy_lr) state in HBM         (base_agent.py:633-639)
+  configure_optimizers()                      Adam / AdamW / SGD(lr=policy_lr) state in HBM (base_agent.py:633-639)
   get_rollout_collector(stage)                DeviceRolloutCollector
 and the fast path the trainer uses instead of per-minibatch Python:
   train_epoch()                               rollout + the whole update phase in one C-ABI call
@@ -25,7 +25,7 @@ import torch
 
 import ctypes
 
-from ._lib import ACT_SLOT, GS_HP_ACT_STATS, GS_HP_BF16, GS_NUM_METRICS, M, PPOGlobal, PPOHparams, RolloutView, RolloutViewU8, check, lib, ptr, stream_handle
+from ._lib import ACT_SLOT, GS_ADAMW_WEIGHT_DECAY, GS_HP_ACT_STATS, GS_HP_BF16, GS_NUM_METRICS, M, OPT_FLAGS, PPOGlobal, PPOHparams, RolloutView, RolloutViewU8, check, lib, ptr, stream_handle
 from .config import device_env_kind
 from .cnn import DeviceCNNActorCritic
 from .policy import DeviceMLPActorCritic
@@ -49,6 +49,18 @@ class MinibatchIndices:
 
     def __len__(self):
         return int(self.idx.numel())
+
+
+def _checkpoint_optimizer(state, opt) -> str:
+    """The optimizer a checkpoint was written under: state.json's name, else (the reference's files,
+    which record none) what optimizer.pt's param group shows."""
+    name = (state or {}).get("optimizer")
+    if name:
+        return str(name).lower()
+    group = ((opt or {}).get("param_groups") or [{}])[0]
+    if "momentum" in group:
+        return "sgd"
+    return "adamw" if group.get("decoupled_weight_decay") else "adam"
 
 
 class DevicePPOAgent:
@@ -226,10 +238,21 @@ class DevicePPOAgent:
         return self._rollout_collectors[stage]
 
     # ---- checkpoints (agents/base_agent.py:658-885) -----------------------------------------
+    @property
+    def optimizer_name(self) -> str:
+        """config.optimizer: "adam", "adamw" or "sgd" (utils/optimizer_factory.py:6-29)."""
+        return str(getattr(self.config, "optimizer", "adam")).lower()
+
     def _adam_state_dicts(self):
-        """Flat HBM moments -> torch.optim.Adam state_dict layout (one entry per tensor in
-        the reference's parameter order)."""
+        """Flat HBM moments -> the state_dict layout of the config's torch optimizer (one entry per
+        tensor in the reference's parameter order): Adam's, AdamW's (Adam's state, a group with the
+        decoupled decay) or SGD's (no state: momentum 0 keeps no buffer)."""
         pm = self.policy_model
+        if self.optimizer_name == "sgd":
+            group = {"lr": float(self.policy_lr), "momentum": 0, "dampening": 0, "weight_decay": 0, "nesterov": False,
+                     "maximize": False, "foreach": None, "differentiable": False, "fused": None,
+                     "params": list(range(len(pm.shapes())))}
+            return [{"state": {}, "param_groups": [group]}]
         to_ref = getattr(pm, "flat_to_reference", None)
         m = to_ref(self.adam_m) if to_ref else self.adam_m.cpu().numpy()
         v = to_ref(self.adam_v) if to_ref else self.adam_v.cpu().numpy()
@@ -243,11 +266,14 @@ class DevicePPOAgent:
         group = {"lr": float(self.policy_lr), "betas": (0.9, 0.999), "eps": 1e-8, "weight_decay": 0,
                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False,
                  "differentiable": False, "fused": None, "params": list(range(len(state)))}
+        if self.optimizer_name == "adamw":
+            group.update(weight_decay=GS_ADAMW_WEIGHT_DECAY, decoupled_weight_decay=True)
         return [{"state": state, "param_groups": [group]}]
 
     def save_checkpoint(self, checkpoint_dir) -> None:
-        """model.pt (reference state_dict keys), optimizer.pt (torch Adam state_dict list),
-        state.json (epoch, counters, config, RNG) — the reference's checkpoint files."""
+        """model.pt (reference state_dict keys), optimizer.pt (the state_dict list of the config's
+        torch optimizer), state.json (epoch, counters, config, RNG, the optimizer's name) — the
+        reference's checkpoint files."""
         import dataclasses
         import json
         import random
@@ -261,7 +287,7 @@ class DevicePPOAgent:
         state = {
             "epoch": int(self.current_epoch),
             "total_env_steps": int(coll.total_steps), "total_vec_steps": int(coll.total_vec_steps),
-            "adam_step": int(self.adam_step), "run_id": None,
+            "adam_step": int(self.adam_step), "run_id": None, "optimizer": self.optimizer_name,
             "config": {k: (list(v) if isinstance(v, tuple) else v) for k, v in dataclasses.asdict(self.config).items()},
             "best_train_reward": float(coll._best_episode_reward),
             # the schedulable hyper-parameters in effect (a resumed run continues from these)
@@ -292,17 +318,24 @@ class DevicePPOAgent:
         if not (resume_training and state):
             return
         opt_path = d / "optimizer.pt"
+        opt = None
         if opt_path.exists():
             opt = torch.load(opt_path, map_location="cpu", weights_only=True)
             opt = opt[0] if isinstance(opt, (list, tuple)) else opt
+        saved = _checkpoint_optimizer(state, opt)
+        if saved != self.optimizer_name:
+            raise ValueError(f"the checkpoint in {str(d)!r} was written under optimizer {saved!r}, this agent runs "
+                             f"{self.optimizer_name!r}: resume with the same config.optimizer")
+        if opt is not None:
             st = opt["state"]
-            m = np.concatenate([np.asarray(st[i]["exp_avg"], np.float32).reshape(-1) for i in sorted(st)])
-            v = np.concatenate([np.asarray(st[i]["exp_avg_sq"], np.float32).reshape(-1) for i in sorted(st)])
-            from_ref = getattr(self.policy_model, "flat_from_reference", None)
-            mt = from_ref(m) if from_ref else torch.as_tensor(m)
-            vt = from_ref(v) if from_ref else torch.as_tensor(v)
-            self.adam_m.copy_(mt.to(self.device))
-            self.adam_v.copy_(vt.to(self.device))
+            if saved != "sgd":      # SGD (momentum 0) keeps no state
+                m = np.concatenate([np.asarray(st[i]["exp_avg"], np.float32).reshape(-1) for i in sorted(st)])
+                v = np.concatenate([np.asarray(st[i]["exp_avg_sq"], np.float32).reshape(-1) for i in sorted(st)])
+                from_ref = getattr(self.policy_model, "flat_from_reference", None)
+                mt = from_ref(m) if from_ref else torch.as_tensor(m)
+                vt = from_ref(v) if from_ref else torch.as_tensor(v)
+                self.adam_m.copy_(mt.to(self.device))
+                self.adam_v.copy_(vt.to(self.device))
             steps = {int(float(st[i]["step"])) for i in st}
             self.adam_step = int(state.get("adam_step", max(steps) if steps else 0))
             groups = opt.get("param_groups") or []
@@ -327,9 +360,9 @@ class DevicePPOAgent:
             random.setstate((r[0], tuple(r[1]), r[2]))
 
     def configure_optimizers(self):
-        """Adam(params, lr=policy_lr) (utils/optimizer_factory.py:6-29): state in HBM."""
-        if str(getattr(self.config, "optimizer", "adam")).lower() != "adam":
-            raise ValueError("device path implements the reference's default optimizer 'adam' only")
+        """Adam / AdamW / SGD(params, lr=policy_lr) by config.optimizer (utils/optimizer_factory.py:6-29):
+        state in HBM.  SGD keeps the two moment buffers too (the entries take the pointers) and never
+        reads them."""
         P = self.policy_model.n_params
         z = dict(dtype=torch.float32, device=self.device)
         self.grads = torch.zeros(P, **z)
@@ -411,6 +444,7 @@ class DevicePPOAgent:
         flags = GS_HP_BF16 if str(getattr(c, "precision", "fp32")) == "bf16" else 0
         if self.device_activation_stats:
             flags |= GS_HP_ACT_STATS
+        flags |= OPT_FLAGS[self.optimizer_name]
         return PPOHparams(float(self.clip_range), float(self.clip_range_vf), float(self.vf_coef), float(self.ent_coef),
                           float(c.max_grad_norm if c.max_grad_norm is not None else 0.0), float(self.policy_lr),
                           0.9, 0.999, 1e-8, float(tkl), 1 if c.normalize_advantages == "batch" else 0, flags)

@@ -25,7 +25,7 @@ from typing import Dict
 import numpy as np
 import torch
 
-from ._lib import GS_NUM_METRICS, M, PGHparams, RolloutView, check, lib, ptr, stream_handle
+from ._lib import GS_NUM_METRICS, M, OPT_FLAGS, PGHparams, RolloutView, check, lib, ptr, stream_handle
 from .ppo_agent import DevicePPOAgent, MinibatchIndices
 from .rollout import DeviceRolloutCollector
 from .samplers import IndexStreamPrefetcher
@@ -91,11 +91,10 @@ class DeviceREINFORCEAgent(DevicePPOAgent):
 
     # ---- optimizer state ----------------------------------------------------------------------
     def configure_optimizers(self):
-        """Adam(params, lr=policy_lr) state in HBM.  The loss never touches the value head: its .grad
-        stays None in the reference, so clip_grad_norm_ and Adam skip it — its moments stay zero here."""
+        """Adam / AdamW / SGD(params, lr=policy_lr) by config.optimizer, state in HBM.  The loss never
+        touches the value head: its .grad stays None in the reference, so clip_grad_norm_ and the
+        optimizer skip it — its moments stay zero here, and AdamW does not decay it."""
         c = self.config
-        if str(getattr(c, "optimizer", "adam")).lower() != "adam":
-            raise ValueError("device path implements the reference's default optimizer 'adam' only")
         P = self.policy_model.n_params
         z = dict(dtype=torch.float32, device=self.device)
         self.grads, self.adam_m, self.adam_v = torch.zeros(P, **z), torch.zeros(P, **z), torch.zeros(P, **z)
@@ -167,7 +166,8 @@ class DeviceREINFORCEAgent(DevicePPOAgent):
     def hparams(self) -> PGHparams:
         c = self.config
         return PGHparams(float(self.ent_coef), float(c.max_grad_norm if c.max_grad_norm is not None else 0.0),
-                         float(self.policy_lr), 0.9, 0.999, 1e-8, 1 if self.normalize_targets else 0, 0)
+                         float(self.policy_lr), 0.9, 0.999, 1e-8, 1 if self.normalize_targets else 0,
+                         OPT_FLAGS[self.optimizer_name])
 
     def _rollout_view(self, buf) -> RolloutView:
         """The update's view: `advantages` carries the policy targets (returns or advantages)."""

@@ -267,6 +267,19 @@ typedef struct gs_ppo_hparams {
  * backbone.2; NatureCNN: cnn.0, cnn.2, cnn.4, mlp.0).  gs_ppo_update / gs_ppo_minibatch_step /
  * gs_cnn_ppo_update; not the global-minibatch entries.  Off: those slots stay 0. */
 #define GS_HP_ACT_STATS 2
+/* The optimizer of the update entries (utils/optimizer_factory.py:6-29: torch's classes at their
+ * defaults but lr).  Neither bit: torch.optim.Adam.  GS_HP_OPT_ADAMW: torch.optim.AdamW — per
+ * parameter p = p * f32(1 - (double)lr * GS_ADAMW_WEIGHT_DECAY), then Adam's step (decoupled decay: a
+ * parameter whose gradient is exactly zero is still decayed, its moments stay 0).  GS_HP_OPT_SGD:
+ * torch.optim.SGD (no momentum, no decay) — p = p + f32(-lr) * g; adam_m / adam_v are neither read nor
+ * written (the pointers are still required) and adam_step only counts the applied steps.  Both run
+ * on the gradient after clip_grad_norm_.  Both bits set: GS_E_INVALID before any launch from every
+ * entry that takes an optimizer step; the *_loss entries ignore the bits; gs_ppo_stage (the Adam
+ * chain's stages) refuses them.  gs_ppo_update runs AdamW / SGD on the fused chain with the separate
+ * clip + step launch (the lagged forward is Adam's). */
+#define GS_HP_OPT_ADAMW 4
+#define GS_HP_OPT_SGD 8
+#define GS_ADAMW_WEIGHT_DECAY 0.01
 
 /* Per-minibatch metric record written by the loss kernel (floats, GS_NUM_METRICS each).
  * KL early stop (agents/base_agent.py:330-366, sticky): the minibatch whose approx_kl exceeds
@@ -470,7 +483,7 @@ typedef struct gs_pg_hparams {
     float adam_beta2;
     float adam_eps;
     int32_t normalize_targets;  /* 1 = "batch" (utils/torch.py:97-99), 0 = off */
-    int32_t flags;              /* GS_HP_BF16 is refused; other bits ignored */
+    int32_t flags;              /* GS_HP_BF16 is refused; GS_HP_OPT_* as above; other bits ignored */
 } gs_pg_hparams;
 size_t gs_pg_update_workspace_bytes(gs_mlp_dims dims, int64_t batch);
 int gs_pg_update(float *params_dev, float *grads_dev, float *adam_m_dev, float *adam_v_dev, gs_mlp_dims dims,
